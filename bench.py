@@ -4,8 +4,22 @@ traversal + ray/sphere tests -> diffuse shading (depth 5, the reference's
 MAX_DEPTH, main.c:19/366) -> RGBA8 framebuffer IN HOST MEMORY (SURVEY §8(d)
 t_frame: the end point of main.c:371-372's display).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: scene and tree, the
+renderer, the untimed priming and warm-up launches, the K timed steps, the
+line (`value`, `ms_per_step`, the schedule in `config`, the last frame's
+SHA-256 and the timed launches' own pass times, which cost no launch).
+`--dump-outputs DIR` writes, after the timed steps, what their last step
+delivered to the caller: the RGBA8 frame in host memory as DIR/frame.npy
+(float32, H x W x 4; a frame past 60 MB as a fixed, seeded sample of its rows,
+their indices in DIR/frame_rows.npy). Scene, camera and RNG seeds are fixed, so
+two builds run with the same arguments can be compared frame for frame.
+Everything below that is measured or checked BESIDE the headline -- the
+device-resident and depth-1 loops, the one-context frame check, the other
+delivery at N > 1, the work counters, the serial launch, the roofline, the
+blocking call, the CPU baseline -- runs only with `--full`.
 
 Every N runs the C-ABI multi-GPU renderer of include/mirt_multi.h -- the
 path a C caller of main.c's loop uses -- in ONE process:
@@ -39,8 +53,8 @@ per launch (1 at N <= 2, 2 at N = 4, 4 at N = 8); `--tail-grid T` puts the burst
 last T launches on the full grid (MIRT_MULTI_FULL_GRID; 0 by default: it
 lost through mirt_multi in round 5's emulation).
 
-Also in the line: `device_resident_mrays_s` (the same loop with the frames
-left in device 0's HBM: the previous rounds' headline), depth 1, the
+Also in the line with `--full`: `device_resident_mrays_s` (the same loop
+with the frames left in device 0's HBM: the previous rounds' headline), depth 1, the
 blocking call per frame (N = 1, a child process holding one context, as
 main.c's loop runs), `roofline` (the bounce kernel on its binding unit, the
 vector-memory gather path; profiles/), `cpu_baseline` (the unmodified
@@ -744,6 +758,27 @@ def last_delivered(m, bufs, launches):
     return bufs[(m.launches - 1) % m.lanes][k - 1].array.copy(), (f0 + k - 1) * SPP
 
 
+DUMP_CAP_B = 60 * 1000 * 1000   # --dump-outputs writes at most this many bytes of array data
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the frame the last timed step delivered, as its caller
+    holds it (H x W x 4 RGBA8 in host memory), written as float32 to
+    `path`/frame.npy. A frame past DUMP_CAP_B (4K) is written as a sample of
+    whole rows, the same every run (drawn once from SEED, ascending), their
+    indices in frame_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    a = np.asarray(frame)
+    row_b = a[0].size * 4 + 8     # a row as float32 + its index as float64
+    if os.path.exists(os.path.join(path, "frame_rows.npy")):
+        os.remove(os.path.join(path, "frame_rows.npy"))     # an earlier, sampled dump's
+    if a.shape[0] * row_b > DUMP_CAP_B:
+        rows = np.sort(np.random.default_rng(SEED).choice(a.shape[0], DUMP_CAP_B // row_b, replace=False))
+        np.save(os.path.join(path, "frame_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, "frame.npy"), a.astype(np.float32))
+
+
 def measure(args):
     """The GPU measurement over args.gpus devices in THIS process. The
     headline delivers every frame to page-locked host memory (SURVEY §8(d)
@@ -767,6 +802,8 @@ def measure(args):
     elapsed = timed_loop(m, cam, warm, timed_launches, bufs, DEPTH, args.accumulate, tail)
     enqueue_ms = [round(float(np.median(ENQUEUE)) * 1e3, 4), round(float(np.max(ENQUEUE)) * 1e3, 4)]
     last_frame, last_sample = last_delivered(m, bufs, timed_launches)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_frame)
     # the passes of rank 0's timed launches (HIP events on each launch's own
     # stream, under the overlap of the lanes in flight)
     phases = []
@@ -775,26 +812,27 @@ def measure(args):
         if k_lane:
             phases += m.phase_log(lane, 0, min(k_lane, 64))
     primary_ms, bounce_ms = (float(v) for v in np.mean(np.array(phases), axis=0)) if phases else (0.0, 0.0)
-    # depth 1 (camera rays and their shading only), frames to host memory, and
-    # (one GPU) the same loop with the frames left on the device
-    el_d1 = timed_loop(m, cam, plan(0, 2, per), plan(args.warmup, args.steps, per), bufs, 1, False, tail)
-    el_d1_dev = None
-    if n == 1:
+    # --full: depth 1 (camera rays and their shading only), frames to host
+    # memory, and (one GPU) the same loop with the frames left on the device
+    el_d1 = el_d1_dev = None
+    if args.full:
+        el_d1 = timed_loop(m, cam, plan(0, 2, per), plan(args.warmup, args.steps, per), bufs, 1, False, tail)
+    if args.full and n == 1:
         el_d1_dev = timed_loop(m, cam, plan(0, 2, per), plan(args.warmup, args.steps, per), bufs, 1, False, tail,
                                device_only=True)
-    # the same loop with the frames left on the device(s): N = 1 in the
-    # rank's slabs; N > 1 gathered on GPU 0 over RCCL (below)
+    # --full: the same loop with the frames left on the device(s): N = 1 in
+    # the rank's slabs; N > 1 gathered on GPU 0 over RCCL (below)
     el_dev = None
-    if n == 1:
+    if args.full and n == 1:
         el_dev = timed_loop(m, cam, plan(0, 2, per), plan(args.warmup, args.steps, per), bufs, DEPTH,
                             args.accumulate, tail, device_only=True)
     m.close()
     close_bufs(bufs)
-    # the last delivered frame against one context rendering the same frame
-    # alone (the N-GPU frame must equal the one-GPU frame byte for byte);
+    # --full: the last delivered frame against one context rendering the same
+    # frame alone (the N-GPU frame must equal the one-GPU frame byte for byte);
     # checked before the other delivery runs, so a failure there cannot cost it
     same = None
-    if not args.accumulate:
+    if args.full and not args.accumulate:
         with mirt.Renderer(0) as r1:
             r1.upload(spheres, bvh)
             one = r1.render_frame(cam, W, H, depth=DEPTH, seed=SEED, sample=last_sample, samples=SPP, jitter=JITTER)
@@ -836,7 +874,7 @@ def measure(args):
         "device_resident_note": ("the same launches with the frames left in device memory (no D2H)" if n == 1 else
                                  "the same launches with every frame gathered on GPU 0 over RCCL and "
                                  "de-interleaved there (no D2H)"),
-        "depth1_mrays_s": round(W * H * SPP * args.steps / el_d1 / 1e6, 3),
+        "depth1_mrays_s": round(W * H * SPP * args.steps / el_d1 / 1e6, 3) if el_d1 else None,
         "depth1_device_resident_mrays_s": round(W * H * SPP * args.steps / el_d1_dev / 1e6, 3) if el_d1_dev else None,
         "depth1_note": "depth 1 through the same loop: frames delivered to page-locked host memory (depth1_mrays_s; "
                        "a 1080p frame's D2H is 0.155 ms at the link's 53.5 GB/s) and left in HBM "
@@ -851,7 +889,14 @@ def measure(args):
                                                "launch issued from this one thread; includes waiting for the "
                                                "lane's previous launch)"},
     }
-    if n > 1:
+    line["full"] = args.full
+    if not args.full:   # a plain run: the legs beside the headline were not run, their keys stay out of the line
+        for k in ("device_resident_mrays_s", "device_resident_note", "depth1_mrays_s",
+                  "depth1_device_resident_mrays_s", "depth1_note", "last_frame_equals_one_context"):
+            del line[k]
+    if args.dump_outputs:
+        line["dumped_outputs"] = args.dump_outputs
+    if n > 1 and args.full:
         line["reference_work"] = multi_reference_work(spheres, bvh, cam, n, elapsed, args.steps)
     if SAME_DEVICE:
         line["rehearsal_same_device"] = "every rank on GPU 0 (copy exchange): a plumbing rehearsal, not a measurement"
@@ -864,7 +909,7 @@ def measure(args):
     # on a multi-GPU node before) is reported in the line, not raised, and its
     # waits are bounded by a shorter timeout so a stuck exchange fails fast.
     other = None
-    if n > 1 and not args.no_other:
+    if n > 1 and args.full and not args.no_other:
         od = "gather" if delivery == "host-direct" else "host-direct"
         other = {"delivery": od}
         m2 = bufs2 = None
@@ -920,7 +965,7 @@ def measure(args):
         line["other_delivery"] = other
     if el_dev:
         line["device_resident_mrays_s"] = round(W * H * SPP * args.steps / el_dev / 1e6, 3)
-    if n == 1:
+    if n == 1 and args.full:
         line.update(single_gpu_extras(args, spheres, bvh, cam, value, elapsed, bounce_ms, primary_ms, per))
     drop_partial()
     print(json.dumps(line), flush=True)
@@ -940,7 +985,7 @@ def save_partial(line, n, args):
     if not path or n == 1:
         return
     part = dict(line)
-    if not args.no_other:
+    if args.full and not args.no_other:
         od = "gather" if part["config"]["delivery"] == "host-direct" else "host-direct"
         part["other_delivery"] = {"delivery": od, "error": "not finished: the measuring process ended in this leg "
                                                            "(terminated at --rank-timeout, or died); this line was "
@@ -1112,9 +1157,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-host", action="store_true", help="skip the blocking-call leg (child process)")
-    ap.add_argument("--no-other", action="store_true", help="N > 1: skip the other delivery's leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured or checked beside the headline: the device-resident and depth-1 "
+                         "loops, the one-context frame check, the other delivery (N > 1), the work counters, the "
+                         "serial launch, the roofline, the blocking call and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the frame their last step delivered as DIR/frame.npy "
+                         "(float32; past 60 MB a fixed, seeded sample of its rows, indices in DIR/frame_rows.npy)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the blocking-call leg (child process)")
+    ap.add_argument("--no-other", action="store_true", help="--full, N > 1: skip the other delivery's leg")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="1080p_10k")
     ap.add_argument("--delivery", choices=("auto", "gather", "host-direct"), default="auto",
                     help="gather: RCCL gather of the slabs to GPU 0, de-interleave, one D2H per frame (SURVEY "

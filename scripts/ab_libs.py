@@ -47,7 +47,7 @@ def main():
             path, _, opts = lib.partition("@")
             env = dict(os.environ, MIRT_LIB=os.path.abspath(path))
             extra = [x for o in opts.split(",") if o for x in ("--opt", o)]
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-host",
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-host",
                                 "--workload", a.workload, "--steps", str(a.steps)] + extra, env=env,
                                capture_output=True, text=True, timeout=600)
             if p.returncode:

@@ -4,7 +4,7 @@ under rocprofv3 --kernel-trace, their mean duration beside the counter pass's
 exclusive time.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<tag>/prof_exclusive -o run -- \
-        python3 bench.py --no-cpu --no-host --pipeline 1 --bounce-blocks 384 --steps 20 --warmup 5
+        python3 bench.py --full --no-cpu --no-host --pipeline 1 --bounce-blocks 384 --steps 20 --warmup 5
     python scripts/exclusive_trace.py gpurun_out/<tag>/prof_exclusive/run_kernel_trace.csv \
         --pmc profiles/r05_pmc_bound_1080p_10k.json --json profiles/r05_exclusive_bounce_trace.json
 """
@@ -26,7 +26,7 @@ def main():
     rows = [r for r in csv.DictReader(open(a.trace)) if BOUNCE in r["Kernel_Name"] and int(r["Grid_Size_X"]) == a.grid]
     ms = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
     pmc = json.load(open(a.pmc))
-    out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu --no-host --pipeline 1 "
+    out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu --no-host --pipeline 1 "
                       "--bounce-blocks 384 --steps 20 --warmup 5",
            "kernel": f"{BOUNCE}, grid {a.grid} work-items (384 workgroups: the timed launch shape), one launch at "
                      "a time",

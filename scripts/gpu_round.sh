@@ -32,12 +32,12 @@ for s in "$@"; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()";;
     tests) step pytest_gpu 900 $PYT tests -m gpu;;
     multi) step pytest_multi 600 $PYT tests/test_multi.py -m gpu -s;;
-    bench) step bench 600 python bench.py;;
-    bench_wl) for wl in 1080p_100k 4k_10k 4k_1m_4spp; do step bench_$wl 600 python bench.py --workload $wl --no-cpu; done;;
+    bench) step bench 600 python bench.py --full;;
+    bench_wl) for wl in 1080p_100k 4k_10k 4k_1m_4spp; do step bench_$wl 600 python bench.py --full --workload $wl --no-cpu; done;;
     # one launch at a time (--pipeline 1): per-kernel durations as bench.py's serial measurement loop sees them
-    prof)  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --no-cpu --no-host --pipeline 1;;
-    pmc)   step pmc_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --no-cpu --no-host --steps 5 --warmup 1 --pipeline 1
-           step pmc_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --no-cpu --no-host --steps 5 --warmup 1 --pipeline 1;;
+    prof)  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --no-cpu --no-host --pipeline 1;;
+    pmc)   step pmc_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --full --no-cpu --no-host --steps 5 --warmup 1 --pipeline 1
+           step pmc_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --full --no-cpu --no-host --steps 5 --warmup 1 --pipeline 1;;
     *) echo "unknown step $s"; exit 2;;
   esac
 done

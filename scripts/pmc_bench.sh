@@ -29,7 +29,7 @@ i=0
 for cs in "${SETS[@]}"; do
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $cs --output-format csv -d "$OUT/bench.$i" -o run -- \
-      python3 bench.py --no-cpu --no-host "$@" > "$OUT/bench.$i.log" 2>&1
+      python3 bench.py --full --no-cpu --no-host "$@" > "$OUT/bench.$i.log" 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "set $i rc=$rc"; grep -m2 -i "error" "$OUT/bench.$i.log"; exit $rc; fi
 done

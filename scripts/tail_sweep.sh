@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for r in $(seq 1 "$R"); do
   for wl in $WLS; do for t in $TAILS; do
     f="$OUT/t_${wl}_tail${t}_$r.log"
-    timeout -k 10 180 python bench.py --no-cpu --no-host --steps 20 --warmup 5 --workload "$wl" --tail-grid "$t" > "$f" 2>&1 || exit $?
+    timeout -k 10 180 python bench.py --full --no-cpu --no-host --steps 20 --warmup 5 --workload "$wl" --tail-grid "$t" > "$f" 2>&1 || exit $?
     v=$(grep -o '"value": [0-9.]*' "$f" | head -1)
     k=$(grep -o '"kernel_ms": [0-9.]*' "$f" | head -1)
     echo "$wl tail $t round $r $v $k" | tee -a "$OUT/summary.txt"

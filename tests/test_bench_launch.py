@@ -74,7 +74,7 @@ def test_stuck_secondary_leg_keeps_the_headline():
     the line the child saved before the leg, the leg marked unfinished, the
     child's exit status in the line, and exits 0 with exactly one line."""
     deadline = 15.0
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--steps", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--full", "--steps", "2",
                         "--warmup", "1", "--rank-timeout", str(deadline)], capture_output=True, text=True,
                        timeout=120, env=_env(MIRT_BENCH_DRY_HANG="after-headline"), cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -131,10 +131,55 @@ def test_bench_line_one_gpu_short():
     """The driver's N = 1 command, short: the headline through mirt_multi
     (RCCL, frames into page-locked host memory), its last frame equal to one
     context's, the device-resident and depth-1 legs beside it."""
-    d = _run("--steps", "8", "--warmup", "2", "--no-cpu", "--no-host", timeout=400)
+    d = _run("--full", "--steps", "8", "--warmup", "2", "--no-cpu", "--no-host", timeout=400)
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["device_resident_mrays_s"] > 0
     assert d["last_frame_equals_one_context"] is True
     assert d["config"]["delivery"] == "gather" and d["depth1_mrays_s"] > 0
+
+
+def test_dump_outputs_samples_a_frame_past_the_cap(tmp_path):
+    """--dump-outputs on a 4K frame (133 MB as float32): whole rows, the same
+    ascending sample on every call, under 64 MB in all; a 1080p frame whole."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frame = (np.arange(2160 * 3840 * 4, dtype=np.uint32) % 251).astype(np.uint8).reshape(2160, 3840, 4)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), frame)
+    bench.dump_outputs(str(b), frame)
+    assert sorted(os.listdir(a)) == ["frame.npy", "frame_rows.npy"]
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 64 * 1000 * 1000
+    rows, got = np.load(a / "frame_rows.npy"), np.load(a / "frame.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and len(rows) == len(got) > 900
+    assert (np.diff(rows) > 0).all() and (got == frame[rows.astype(int)]).all()
+    assert (np.load(b / "frame_rows.npy") == rows).all() and (np.load(b / "frame.npy") == got).all()
+    bench.dump_outputs(str(b), frame[:1080, :1920])
+    assert np.load(b / "frame.npy").shape == (1080, 1920, 4) and os.listdir(b) == ["frame.npy"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_last_frame(tmp_path):
+    """A plain run: the headline alone (none of --full's legs in the line),
+    --steps timed steps, and --dump-outputs writes the last step's frame as
+    float32, the very bytes whose SHA-256 the line carries."""
+    import hashlib
+
+    import numpy as np
+    out = tmp_path / "dump"
+    d = _run("--steps", "4", "--warmup", "1", "--dump-outputs", str(out))
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 4 and d["config"]["launches"] == 4
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mrays/s" and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(1920 * 1080 / d["ms_per_step"] / 1e3, rel=1e-3)
+    for k in ("depth1_mrays_s", "device_resident_mrays_s", "roofline", "cpu_baseline", "host_blocking_mrays_s",
+              "last_frame_equals_one_context", "work"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    f = np.load(out / "frame.npy")
+    assert f.dtype == np.float32 and f.shape == (1080, 1920, 4)
+    assert hashlib.sha256(f.astype(np.uint8).tobytes()).hexdigest() == d["frame_sha_last"]
 
 
 @pytest.mark.gpu
@@ -144,7 +189,8 @@ def test_bench_line_two_ranks_same_device_rehearsal():
     RCCL): the measuring child, the host-direct headline, the gather leg
     beside it and the one-lane check, every checked frame equal to one
     context's; the line is marked as a rehearsal."""
-    d = _run("--gpus", "2", "--same-device", "--steps", "8", "--warmup", "2", "--no-cpu", "--no-host", timeout=400)
+    d = _run("--gpus", "2", "--same-device", "--full", "--steps", "8", "--warmup", "2", "--no-cpu", "--no-host",
+             timeout=400)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["rehearsal_same_device"]
     assert d["config"]["delivery"] == "host-direct" and d["last_frame_equals_one_context"] is True
     o = d["other_delivery"]
