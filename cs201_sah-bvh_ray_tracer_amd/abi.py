@@ -159,6 +159,8 @@ SIGNATURES = [
     ("mirt_any_hit_rays", I, [P, P, I, I, P]),
     ("mirt_sphere_pairs", I, [P, P, P, I, P]),
     ("mirt_aabb_pairs", I, [P, P, P, I, P]),
+    ("mirt_box_form_pairs", I, [P, P, P, P, I, I, P]),
+    ("mirt_sphere_form_pairs", I, [P, P, P, P, I, I, P]),
     ("mirt_camera_rays", I, [P, P, P, P]),
     ("mirt_count_frame", I, [P, P, P, P]),
     ("mirt_wave_stats", I, [P, P, P, P, I]),
@@ -207,6 +209,7 @@ OPT_TRAVERSAL, OPT_FAST_SLAB, OPT_BLOCK_WAVES, OPT_DEFER, OPT_BOUNCE_THRESHOLD, 
 OPT_BOUNCE_BLOCKS, OPT_QUAD_DRAIN, OPT_LEAF_BATCH, OPT_QUAD_BATCH, OPT_ZERO_COPY = 9, 11, 14, 15, 17
 OPT_QUEUE_ORDER, OPT_DEBUG_STALL_MS = 18, 19
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
+BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4
 MULTI_COPY, MULTI_HOST_DIRECT, MULTI_QUEUE_AHEAD = 1, 2, 4
 MULTI_FULL_GRID = 1
 MULTI_OPT_TIMEOUT_MS, MULTI_OPT_EMULATE_WORLD, MULTI_OPT_EMULATE_RANK, MULTI_OPT_DIRECT_COPY = 256, 257, 258, 259

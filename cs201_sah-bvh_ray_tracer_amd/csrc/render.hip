@@ -503,14 +503,25 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
 // slab_cons_fast's margins (trace.h, BND): the boxes are grown by 2^-19
 // DevScene::o_bound at upload, and a bounce ray whose origin lies within that
 // bound -- a hit point in the scene -- needs no more; an origin beyond it (or
-// NaN) takes the exact test. Round 6: serial bounce pass 0.84-0.86 ->
+// NaN) takes the exact test, and so does every ray of a scene without a bound
+// (o_bound == 0: its boxes were never grown, and an origin of exactly zero
+// would otherwise pass max|o| <= 0). Round 6: serial bounce pass 0.84-0.86 ->
 // 0.83 ms, 1080p/10k +1.5-3%, 1080p/100k +3.5% (MEASUREMENTS.md §D).
 constexpr bool kBoundedSlab = true;
 __device__ __forceinline__ SlabRay bounce_slab_ray(const DevScene& sc, const Ray& ray)
 {
     SlabRay s = slab_ray(ray);
-    s.generic = s.generic || !(fmaxf(fabsf(ray.ox), fmaxf(fabsf(ray.oy), fabsf(ray.oz))) <= sc.o_bound);
+    s.generic = s.generic ||
+                !(sc.o_bound > 0.0f && fmaxf(fabsf(ray.ox), fmaxf(fabsf(ray.oy), fabsf(ray.oz))) <= sc.o_bound);
     return s;
+}
+
+// The camera rays' form of that rule (trace.h slab_cons_fast<BND>: an origin
+// within 4C still fits the growth), decided once per frame on the host
+// (camera_bounded).
+__host__ __device__ inline bool origin_within_4c(float o_bound, float o_inf)
+{
+    return o_bound > 0.0f && o_inf <= 4.0f * o_bound;
 }
 
 // The walk of one bounce ray: WALK 0 = reference DFS order (any tree),
@@ -1132,6 +1143,66 @@ __global__ void aabb_pairs_kernel(const mirt_ray* __restrict__ rays, const mirt_
     const Ray ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
     const mirt_aabb b = boxes[i];
     out[i] = slab_test(slab_ray(ray), b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z) ? 1 : 0;
+}
+
+// The walks' filtered box tests on pairs (mirt_box_form_pairs): the Prune
+// state a walk holds with a best hit at best[i] (none yet: +inf), then the
+// call the walk makes for that kind of box.
+__global__ void box_form_pairs_kernel(DevScene sc, const mirt_ray* __restrict__ rays,
+                                      const mirt_aabb* __restrict__ boxes, const float* __restrict__ best, int n,
+                                      int form, int32_t* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const mirt_ray rr = rays[i];
+    const Ray ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
+    const mirt_aabb b = boxes[i];
+    const float bt = best[i];
+    Prune pr = prune_start(sc, ray.ox, ray.oy, ray.oz);
+    if (sc.prune && bt < INFINITY) prune_update(pr, sc, ray.ox, ray.oy, ray.oz, sph_ray(ray).a4(), bt);
+    SlabRay sr = slab_ray(ray);
+    float near = 0.0f;
+    bool pass = false;
+    switch (form) {
+    case MIRT_BOX_FORM_SLAB: {
+        NodeV nd;
+        nd.b0 = b.min.x; nd.b1 = b.min.y; nd.b2 = b.min.z; nd.b3 = b.max.x; nd.b4 = b.max.y; nd.b5 = b.max.z;
+        nd.sphere = -1;
+        nd.skip = 0;
+        nd.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        pass = slab<true>(sr, pr, nd);
+        break;
+    }
+    case MIRT_BOX_FORM_SLAB_BOX:
+        pass = slab_box<true>(sr, pr, b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z, near);
+        break;
+    case MIRT_BOX_FORM_CONS:
+        pass = slab_cons<false>(sr, pr, b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z, near);
+        break;
+    case MIRT_BOX_FORM_CONS_BOUNCE:
+        sr = bounce_slab_ray(sc, ray);
+        pass = slab_cons<true>(sr, pr, b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z, near);
+        break;
+    default:  // MIRT_BOX_FORM_CONS_CAMERA
+        sr.generic = sr.generic ||
+                     !origin_within_4c(sc.o_bound, fmaxf(fabsf(ray.ox), fmaxf(fabsf(ray.oy), fabsf(ray.oz))));
+        pass = slab_cons<true>(sr, pr, b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z, near);
+        break;
+    }
+    out[i] = pass ? 1 : 0;
+}
+
+// sphere_t<FAST> on pairs (mirt_sphere_form_pairs): the returned float's bits
+template <bool FAST>
+__global__ void sphere_form_pairs_kernel(const mirt_ray* __restrict__ rays, const mirt_sphere* __restrict__ sph,
+                                         const float* __restrict__ best, int n, uint32_t* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const mirt_ray rr = rays[i];
+    const Ray ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
+    const float4 g = make_float4(sph[i].center.x, sph[i].center.y, sph[i].center.z, sph[i].radius);
+    out[i] = __float_as_uint(sphere_t<FAST>(sph_ray(ray), g, best[i]));
 }
 
 __global__ void camera_rays_kernel(FrameConst f, mirt_ray* __restrict__ out)
@@ -1865,7 +1936,7 @@ int launch_render(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_ac
 bool camera_bounded(const mirt_ctx* c, const FrameConst& f)
 {
     const float o = std::max(std::fabs(f.px), std::max(std::fabs(f.py), std::fabs(f.pz)));
-    return c->o_bound > 0.0f && o <= 4.0f * c->o_bound;
+    return origin_within_4c(c->o_bound, o);
 }
 
 int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s, bool timed,
@@ -2922,6 +2993,67 @@ int mirt_aabb_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_aabb* boxes, i
     HIP_TRY(hipMemcpyAsync(din + rb, boxes, bb, hipMemcpyHostToDevice, c->stream));
     aabb_pairs_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const mirt_ray*)din, (const mirt_aabb*)(din + rb), n,
                                                              (int32_t*)c->d_res);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_box_form_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_aabb* boxes, const float* best, int n, int form,
+                        int32_t* out)
+{
+    if (!ctx_ok(c, true, "mirt_box_form_pairs")) return MIRT_E_NOSCENE;
+    if (n < 0 || form < MIRT_BOX_FORM_SLAB || form > MIRT_BOX_FORM_CONS_CAMERA ||
+        (n > 0 && (!rays || !boxes || !best || !out))) {
+        set_error("mirt_box_form_pairs: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    if (n == 0) return MIRT_OK;
+    const size_t rb = sizeof(mirt_ray) * (size_t)n, bb = sizeof(mirt_aabb) * (size_t)n, fb = 4 * (size_t)n;
+    int rc = ensure(&c->d_in, &c->in_cap, rb + bb + fb + 16);
+    if (!rc) rc = ensure(&c->d_res, &c->res_cap, 4 * (size_t)n);
+    if (rc) return rc;
+    char* din = (char*)c->d_in;
+    HIP_TRY(hipMemcpyAsync(din, rays, rb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + rb, boxes, bb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + rb + bb, best, fb, hipMemcpyHostToDevice, c->stream));
+    box_form_pairs_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(dev_scene(c), (const mirt_ray*)din,
+                                                                 (const mirt_aabb*)(din + rb),
+                                                                 (const float*)(din + rb + bb), n, form,
+                                                                 (int32_t*)c->d_res);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_sphere_form_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_sphere* spheres, const float* best, int n,
+                           int fast, uint32_t* out)
+{
+    if (!ctx_ok(c, false, "mirt_sphere_form_pairs")) return MIRT_E_INVALID;
+    if (n < 0 || (n > 0 && (!rays || !spheres || !best || !out))) {
+        set_error("mirt_sphere_form_pairs: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    if (n == 0) return MIRT_OK;
+    const size_t rb = sizeof(mirt_ray) * (size_t)n, sb = sizeof(mirt_sphere) * (size_t)n, fb = 4 * (size_t)n;
+    int rc = ensure(&c->d_in, &c->in_cap, rb + sb + fb + 16);
+    if (!rc) rc = ensure(&c->d_res, &c->res_cap, 4 * (size_t)n);
+    if (rc) return rc;
+    char* din = (char*)c->d_in;
+    HIP_TRY(hipMemcpyAsync(din, rays, rb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + rb, spheres, sb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + rb + sb, best, fb, hipMemcpyHostToDevice, c->stream));
+    const dim3 grid((n + 255) / 256);
+    if (fast)
+        sphere_form_pairs_kernel<true><<<grid, 256, 0, c->stream>>>((const mirt_ray*)din, (const mirt_sphere*)(din + rb),
+                                                                   (const float*)(din + rb + sb), n,
+                                                                   (uint32_t*)c->d_res);
+    else
+        sphere_form_pairs_kernel<false><<<grid, 256, 0, c->stream>>>((const mirt_ray*)din,
+                                                                    (const mirt_sphere*)(din + rb),
+                                                                    (const float*)(din + rb + sb), n,
+                                                                    (uint32_t*)c->d_res);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -329,7 +329,9 @@ __device__ __forceinline__ Prune prune_start(const DevScene& sc, float ox, float
 __device__ __forceinline__ void prune_update(Prune& p, const DevScene& sc, float ox, float oy, float oz, float a4,
                                              float best)
 {
-    const float dl = __builtin_amdgcn_sqrtf(a4) * (0.5f + 0x1p-20f);  // >= |d|
+    // >= |d|. v_sqrt_f32 reads a subnormal input as zero, which bounds nothing
+    // (|d| < 2^-64): such a ray keeps the growth m0, valid for any hit.
+    const float dl = a4 >= 0x1p-126f ? __builtin_amdgcn_sqrtf(a4) * (0.5f + 0x1p-20f) : INFINITY;
     const float oi = fmaxf(fabsf(ox), fmaxf(fabsf(oy), fabsf(oz)));
     p.m = fminf((best * dl + sc.r_max) * 0x1p-8f + (oi + sc.c_max) * 0x1p-20f, prune_m0(sc, ox, oy, oz));
     p.lim = best + best * 0x1p-18f;
@@ -522,6 +524,14 @@ __device__ __forceinline__ SphRay sph_ray(const Ray& r) { return {r.ox, r.oy, r.
 // so |t' - t| < 8u (|b| + s') / 2a, and M = 2^-18 (|b| + s') |1/(2a)| bounds
 // that 8x over. If t' - M > best the recorded t would exceed best (cannot
 // win); if t' + M <= EPS it would fail t > EPS. Otherwise the exact path runs.
+// The bound needs a normal-range disc: v_sqrt_f32 reads a subnormal as zero,
+// and with |b| as small (|d| below 2^-60) the lost sqrt(disc) < 2^-63 is more
+// than M of |b| -- the estimate then ruled out hits at t = best exactly
+// (tests/test_filtered_forms.py, REGRESSION_SUBNORMAL_DISC). A subnormal disc
+// decides nothing here. (A subnormal 2a makes v_rcp_f32 return inf and a
+// 1/(2a) below the normal range 0: the first turns t' - M and t' + M into NaN,
+// which decide nothing; the second needs |b| > 2^105 for a t above EPS, where
+// b b overflows and disc is inf or NaN -- NaN again, or the miss hit.c sees.)
 template <bool FAST>
 __device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best)
 {
@@ -534,7 +544,7 @@ __device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best)
         const float sq = __builtin_amdgcn_sqrtf(disc);
         const float te = (-b - sq) * r.inv2a();
         const float m = (fabsf(b) + sq) * fabsf(r.inv2a()) * 0x1p-18f;
-        if (te - m > best || te + m <= kEps) return -1.0f;
+        if ((te - m > best || te + m <= kEps) && disc >= 0x1p-126f) return -1.0f;
     }
     // hit.c:28 in double: (-b - sqrt(disc)) / (2a), rounded to float
     const double num = (double)(-b) - __dsqrt_rn((double)disc);
@@ -1598,6 +1608,12 @@ __device__ __forceinline__ void hemisphere(uint64_t key, uint32_t& k, const floa
     }
 }
 
+// (int) of a float as the reference's x86 build converts it:
+// a value at or above 2^31 gives 0x80000000 there, where v_cvt_i32_f32
+// saturates to 0x7fffffff (below -2^31 and for NaN the low byte is 0 on both).
+// Only a caller's unnormalised direction (|d| above 1e7) gets there.
+__device__ __forceinline__ int int_x86(float v) { return v >= 0x1p31f ? (int)0x80000000u : (int)v; }
+
 // renderer.c:65-70 sky gradient (float, truncated to Uint8).
 __device__ __forceinline__ uint32_t sky_rgba(float dy)
 {
@@ -1605,7 +1621,7 @@ __device__ __forceinline__ uint32_t sky_rgba(float dy)
     const float omt = 1.0f - t;
     const float r = omt * 255.0f + t * 128.0f;
     const float g = omt * 255.0f + t * 178.0f;
-    return (uint32_t)((int)r & 0xff) | ((uint32_t)((int)g & 0xff) << 8) | (255u << 16) | (255u << 24);
+    return (uint32_t)(int_x86(r) & 0xff) | ((uint32_t)(int_x86(g) & 0xff) << 8) | (255u << 16) | (255u << 24);
 }
 
 // renderer.c:56-58: (Uint8)(base + 0.5 * refl) computed in double and

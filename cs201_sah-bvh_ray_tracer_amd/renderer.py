@@ -427,6 +427,33 @@ class Renderer:
         check(self.L.mirt_aabb_pairs(self.h, ptr(rays), ptr(boxes), len(rays), ptr(out)), "mirt_aabb_pairs")
         return out
 
+    # ---- diagnostics: the walks' filtered tests on pairs
+    def box_form_pairs(self, rays, boxes, best, form):
+        """int32 per pair: 1 if the walks' box test `form` (abi.BOX_FORM_*)
+        passes box i for ray i with a best hit so far of best[i] (+inf: none),
+        under the uploaded scene's pruning state and origin bound."""
+        rays = np.ascontiguousarray(rays, abi.RAY)
+        boxes = np.ascontiguousarray(boxes, abi.AABB)
+        best = np.ascontiguousarray(best, np.float32)
+        assert len(boxes) == len(rays) and len(best) == len(rays)
+        out = np.zeros(len(rays), np.int32)
+        check(self.L.mirt_box_form_pairs(self.h, ptr(rays), ptr(boxes), ptr(best), len(rays), form, ptr(out)),
+              "mirt_box_form_pairs")
+        return out
+
+    def sphere_form_pairs(self, rays, spheres, best, fast=True):
+        """float32 per pair: what the walks' sphere test returns for a best hit
+        so far of best[i] (t if sphere i would become the closest hit, else
+        -1), from the filtered test (fast) or the exact one."""
+        rays = np.ascontiguousarray(rays, abi.RAY)
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        best = np.ascontiguousarray(best, np.float32)
+        assert len(spheres) == len(rays) and len(best) == len(rays)
+        out = np.zeros(len(rays), np.uint32)
+        check(self.L.mirt_sphere_form_pairs(self.h, ptr(rays), ptr(spheres), ptr(best), len(rays), int(fast),
+                                            ptr(out)), "mirt_sphere_form_pairs")
+        return out.view(np.float32)
+
 
 class MultiRenderer:
     """One frame loop over several GPUs from this process (include/mirt_multi.h,

@@ -13,6 +13,10 @@
  * result in host memory; *_device calls enqueue on the given HIP stream.
  * Errors: negative status, message in mirt_last_error(); the library never
  * aborts and never falls back to a CPU path.
+ *
+ * Diagnostic surface (for the test suite; may change between releases):
+ * mirt_box_form_pairs and mirt_sphere_form_pairs run the walks' filtered box
+ * and sphere tests on caller-given pairs.
  */
 #ifndef MIRT_H
 #define MIRT_H
@@ -318,6 +322,30 @@ int mirt_any_hit_rays(mirt_ctx *ctx, const mirt_ray *rays, int n, int use_bvh, i
    (hit.c:49-82) on pairs; need no scene. */
 int mirt_sphere_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_sphere *spheres, int n, mirt_hit *out);
 int mirt_aabb_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_aabb *boxes, int n, int32_t *out);
+
+/* Diagnostic surface (tests; not part of the stable ABI): the walks' FILTERED
+   forms of the two tests above on pairs -- the same device functions the
+   kernels call, so their error bounds can be checked pair by pair against
+   hit.c. The box forms need an uploaded scene: the pruning state comes from its
+   largest radius / coordinate and MIRT_OPT_PRUNE as in the walks (none with
+   pruning off; the start state for best[i] = +inf; else the state after a hit
+   at t = best[i]), the origin bound of the margin-free forms from its boxes.
+   mirt_box_form_pairs: out[i] = 1 if `form` passes box i for ray i.
+   mirt_sphere_form_pairs: out[i] = the bits of the float the sphere test
+   returns for a best hit so far of best[i] (t when the sphere would become
+   the closest hit, else -1), from the filtered test (fast != 0) or the exact
+   one. */
+enum { MIRT_BOX_FORM_SLAB = 0,        /* leaf / node boxes: reciprocal filter, exact when undecided */
+       MIRT_BOX_FORM_SLAB_BOX = 1,    /* the same with the pruning test for zero-component rays */
+       MIRT_BOX_FORM_CONS = 2,        /* inner boxes: conservative, with margins */
+       MIRT_BOX_FORM_CONS_BOUNCE = 3, /* margin-free on grown boxes; a ray whose origin lies beyond the scene's bound C
+                                         (or any ray when the scene has none) takes the exact test, as a bounce ray */
+       MIRT_BOX_FORM_CONS_CAMERA = 4  /* the same under the camera rays' rule, |o| <= 4C (a frame whose camera lies
+                                         beyond it uses MIRT_BOX_FORM_CONS) */ };
+int mirt_box_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_aabb *boxes, const float *best, int n,
+                        int form, int32_t *out);
+int mirt_sphere_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_sphere *spheres, const float *best,
+                           int n, int fast, uint32_t *out);
 
 /* The camera ray of every pixel of the shard (ray.c:17-32 with the pixel
    mapping of main.c:356-365). */
