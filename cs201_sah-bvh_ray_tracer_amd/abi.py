@@ -86,6 +86,12 @@ class Counts(C.Structure):
                 ("hits_primary", C.c_uint64)]
 
 
+class BuildStats(C.Structure):
+    """mirt_build_stats"""
+    _fields_ = [("on_device", C.c_int32), ("levels", C.c_int32), ("nodes", C.c_int32),
+                ("device_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 class MultiStats(C.Structure):
     """mirt_multi_stats (include/mirt_multi.h)"""
     _fields_ = [("launches", C.c_uint64), ("comm_inits", C.c_uint64), ("rccl_groups", C.c_uint64),
@@ -140,6 +146,9 @@ SIGNATURES = [
     ("mirt_destroy", None, [P]),
     ("mirt_scene_upload", I, [P, P, I, P]),
     ("mirt_scene_upload_flat", I, [P, P, I, P, I]),
+    ("mirt_bvh_build_flat_device", I, [P, P, I, I, I, C.POINTER(P), C.POINTER(I)]),
+    ("mirt_last_build_stats", I, [P, P]),
+    ("mirt_build_partition_probe", I, [P, P, I, P, I, P, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),

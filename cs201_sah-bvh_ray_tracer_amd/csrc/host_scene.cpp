@@ -65,7 +65,7 @@ int shard_row_count(const mirt_frame_desc* fd)
 
 extern "C" {
 
-const char* mirt_version(void) { return "mirt 0.6 (gfx950)"; }
+const char* mirt_version(void) { return "mirt 0.7 (gfx950)"; }
 const char* mirt_last_error(void) { return mirt::g_err; }
 
 // ------------------------------------------------------------------ rand

@@ -1443,6 +1443,7 @@ struct mirt_ctx {
     size_t keys_cap = 0;
     int num_cus = 0;
     int debug_stall_ms = 0;     // MIRT_OPT_DEBUG_STALL_MS: test hook, each frame starts behind a bounded wait
+    mirt::BuildState* build = nullptr;  // mirt_bvh_build_flat_device's scratch (bvh_device.hip)
 };
 
 namespace {
@@ -2189,6 +2190,7 @@ void mirt_destroy(mirt_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->slab_guard) (void)hipEventSynchronize(c->slab_free);   // another stream's read of the slab
     accum_release(c->acc);
+    mirt::build_state_free(c->build);
     for (void* p : {(void*)c->d_nodes, (void*)c->d_nodes32, (void*)c->d_geo, (void*)c->d_color, (void*)c->d_out,
                     c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue, (void*)c->d_keys, (void*)c->d_pnodes,
                     (void*)c->d_hnodes, (void*)c->d_haux, (void*)c->d_leaves, (void*)c->d_ndepth,
@@ -2449,6 +2451,7 @@ int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_d
     return enqueue_frame(c, cam, fd, d_out, d_display, fn, independent);
 }
 int ctx_device(const mirt_ctx* c) { return c->device; }
+BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 }  // namespace mirt
 
 extern "C" {

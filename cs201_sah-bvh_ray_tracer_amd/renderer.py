@@ -256,6 +256,31 @@ class Renderer:
             check(self.L.mirt_scene_upload(self.h, ptr(spheres), len(spheres), bvh), "mirt_scene_upload")
         self.num_spheres = len(spheres)
 
+    def build_bvh(self, spheres, start=0, end=None, depth=0):
+        """build_bvh on this context's device (mirt_bvh_build_flat_device): the
+        same Bvh and the same in-place reordering of `spheres`, bit for bit.
+        Needs no uploaded scene; last_build_stats() says how it went."""
+        assert spheres.dtype == abi.SPHERE and spheres.flags["C_CONTIGUOUS"]
+        end = len(spheres) if end is None else end
+        out = C.c_void_p()
+        cnt = C.c_int()
+        check(self.L.mirt_bvh_build_flat_device(self.h, ptr(spheres), start, end, depth, C.byref(out), C.byref(cnt)),
+              "mirt_bvh_build_flat_device")
+        try:
+            buf = (C.c_char * (cnt.value * abi.NODE.itemsize)).from_address(out.value)
+            nodes = np.frombuffer(bytes(buf), dtype=abi.NODE).copy()
+        finally:
+            self.L.mirt_bvh_free_flat(out)
+        return Bvh(nodes)
+
+    def last_build_stats(self):
+        """mirt_build_stats of the last build_bvh on this context, as a dict:
+        on_device (0: the input was declined and the host builder ran), levels,
+        nodes, device_ms (the kernels), total_ms (call to return)."""
+        st = abi.BuildStats()
+        check(self.L.mirt_last_build_stats(self.h, C.byref(st)), "mirt_last_build_stats")
+        return {k: getattr(st, k) for k, _ in abi.BuildStats._fields_}
+
     # ---- frames
     def render_frame(self, cam, width, height, depth=5, use_bvh=True, seed=1, sample=0, accumulate=False,
                      frames=1, row_block=8, shard=0, num_shards=1, samples=1, jitter=False):
@@ -453,6 +478,20 @@ class Renderer:
         check(self.L.mirt_sphere_form_pairs(self.h, ptr(rays), ptr(spheres), ptr(best), len(rays), int(fast),
                                             ptr(out)), "mirt_sphere_form_pairs")
         return out.view(np.float32)
+
+    def partition_probe(self, centre, seg, split):
+        """The device build's partition on caller-given keys: segments
+        [seg[k], seg[k+1]) of `centre`, each partitioned by centre < split[k];
+        returns int32 perm, perm[j] = source index of the element that ends at
+        position j (bvh.c:172-201's swap loop)."""
+        centre = np.ascontiguousarray(centre, np.float32)
+        seg = np.ascontiguousarray(seg, np.int32)
+        split = np.ascontiguousarray(split, np.float32)
+        assert len(seg) == len(split) + 1
+        perm = np.zeros(len(centre), np.int32)
+        check(self.L.mirt_build_partition_probe(self.h, ptr(centre), len(centre), ptr(seg), len(split), ptr(split),
+                                                ptr(perm)), "mirt_build_partition_probe")
+        return perm
 
 
 class MultiRenderer:

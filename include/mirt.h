@@ -16,7 +16,8 @@
  *
  * Diagnostic surface (for the test suite; may change between releases):
  * mirt_box_form_pairs and mirt_sphere_form_pairs run the walks' filtered box
- * and sphere tests on caller-given pairs.
+ * and sphere tests on caller-given pairs; mirt_build_partition_probe runs the
+ * device build's partition on caller-given keys.
  */
 #ifndef MIRT_H
 #define MIRT_H
@@ -222,6 +223,33 @@ int mirt_scene_upload(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres
 int mirt_scene_upload_flat(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres,
                            const mirt_node *nodes, int num_nodes);
 
+/* ------------------------------------------- device: BVH (bit-identical) */
+
+/* mirt_bvh_build_flat on the device of ctx (mirt 0.7): same tree, same in-place
+   reordering of spheres[start,end), bit for bit. *out_nodes is malloc'd
+   (mirt_bvh_free_flat). Needs no uploaded scene and leaves an uploaded one
+   alone. Blocking; the scratch it needs stays with the ctx until mirt_destroy.
+   Arguments are checked as mirt_bvh_build_flat checks them; a NULL ctx is
+   MIRT_E_INVALID before any HIP call, a HIP failure MIRT_E_DEVICE.
+   Declined inputs: the kernels combine boxes in no fixed order, which gives the
+   host's bits only where min/max are exact and symmetric. A range holding a NaN
+   or infinite centre or radius, or a sphere whose box fl(c - r), fl(c + r) has a
+   coordinate equal to -0.0 (fmin(-0, +0) depends on operand order), is
+   detected by the first pass; the host builder then runs on the untouched
+   input (mirt_build_stats.on_device = 0), so the result is the same either way. */
+int mirt_bvh_build_flat_device(mirt_ctx *ctx, mirt_sphere *spheres, int start, int end, int depth,
+                               mirt_node **out_nodes, int *out_count);
+
+typedef struct mirt_build_stats {
+    int32_t on_device;   /* 1: built by the kernels; 0: input declined, host builder ran */
+    int32_t levels;      /* tree levels processed (0 when on_device == 0) */
+    int32_t nodes;
+    float   device_ms;   /* HIP-event time of the build's kernels (0 when on_device == 0) */
+    float   total_ms;    /* call to return, host clock: H2D + kernels + D2H */
+} mirt_build_stats;
+/* Of the ctx's last finished mirt_bvh_build_flat_device (MIRT_E_INVALID: none). */
+int mirt_last_build_stats(mirt_ctx *ctx, mirt_build_stats *out);
+
 /* ---------------------------------------------------------- rendering */
 
 /* Number of rows (and the row indices, if rows != NULL) a shard renders. */
@@ -346,6 +374,13 @@ int mirt_box_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_aabb *bo
                         int form, int32_t *out);
 int mirt_sphere_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_sphere *spheres, const float *best,
                            int n, int fast, uint32_t *out);
+/* The device build's partition kernels on caller-given keys (needs no scene):
+   nseg segments [seg[k], seg[k+1]) of centre[0,n) (seg non-decreasing, within
+   [0, n]), each partitioned by centre < split[k] as bvh.c:172-201's swap loop
+   leaves it; perm[j] = source index of the element that ends at position j
+   (j itself outside the segments). */
+int mirt_build_partition_probe(mirt_ctx *ctx, const float *centre, int n, const int32_t *seg, int nseg,
+                               const float *split, int32_t *perm);
 
 /* The camera ray of every pixel of the shard (ray.c:17-32 with the pixel
    mapping of main.c:356-365). */
