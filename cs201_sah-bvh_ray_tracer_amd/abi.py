@@ -23,8 +23,25 @@ CAMERA = np.dtype([("position", *VEC3), ("forward", *VEC3), ("right", *VEC3), ("
 NODE_EMPTY = 0x80000000
 SKIP_MASK = 0x7FFFFFFF
 
+# The device layouts of csrc/layout.h (mirt_scene_layout returns them).
+GEO = np.dtype(("<f4", (4,)))                                                        # 16 B: centre.xyz, radius
+DNODE = np.dtype([("bmin", *VEC3), ("bmax", *VEC3), ("sphere", "<i4"), ("skip", "<u4"),
+                  ("geo", "<f4", (4,)), ("pad", "<u4", (4,))])                        # 64 B
+PNODE = np.dtype([("c0", "<f4", (6,)), ("c1", "<f4", (6,)), ("ref0", "<u4"), ("ref1", "<u4"),
+                  ("flat", "<u4"), ("end", "<u4")])                                   # 64 B
+HSLOT = np.dtype([("box", "<u4", (3,)), ("ref", "<u4")])       # box: fp16 lo | fp16 hi << 16 per axis
+HNODE = np.dtype([("slot", HSLOT, (4,))])                                             # 64 B
+HAUX = np.dtype([("flat", "<u4"), ("end", "<u4")])                                    # 8 B
+LEAFBOX = np.dtype([("lo", *VEC3), ("hi", *VEC3), ("sphere", "<i4"), ("pad", "<u4")])  # 32 B
+P_LEAF, P_NONE, P_INDEX = 0x80000000, 0xFFFFFFFF, 0x7FFFFFFF
+# MIRT_LAYOUT_* part ids, in order, with the dtype of each part's elements
+LAYOUT_PARTS = [("dnodes", DNODE), ("geo", GEO), ("color", np.dtype("<u4")), ("pnodes", PNODE), ("hnodes", HNODE),
+                ("haux", HAUX), ("leaf_geo", GEO), ("leaf_box", LEAFBOX), ("ndepth", np.dtype("u1"))]
+
 assert SPHERE.itemsize == 20 and RAY.itemsize == 24 and AABB.itemsize == 24
 assert HIT.itemsize == 40 and NODE.itemsize == 32 and CAMERA.itemsize == 64
+assert DNODE.itemsize == 64 and PNODE.itemsize == 64 and HNODE.itemsize == 64 and HAUX.itemsize == 8
+assert LEAFBOX.itemsize == 32 and GEO.itemsize == 16
 
 
 class Vec3(C.Structure):
@@ -92,6 +109,14 @@ class BuildStats(C.Structure):
                 ("device_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class SceneLayoutInfo(C.Structure):
+    """mirt_scene_layout_info"""
+    _fields_ = [("encloses", C.c_int32), ("ordered", C.c_int32), ("leaf_big", C.c_int32),
+                ("r_max", C.c_float), ("c_max", C.c_float), ("o_bound", C.c_float),
+                ("num_pnodes", C.c_uint32), ("num_hnodes", C.c_uint32), ("num_leaves", C.c_uint32),
+                ("wide_root", C.c_uint32), ("leaf_box_off", C.c_uint64)]
+
+
 class MultiStats(C.Structure):
     """mirt_multi_stats (include/mirt_multi.h)"""
     _fields_ = [("launches", C.c_uint64), ("comm_inits", C.c_uint64), ("rccl_groups", C.c_uint64),
@@ -149,6 +174,7 @@ SIGNATURES = [
     ("mirt_bvh_build_flat_device", I, [P, P, I, I, I, C.POINTER(P), C.POINTER(I)]),
     ("mirt_last_build_stats", I, [P, P]),
     ("mirt_build_partition_probe", I, [P, P, I, P, I, P, P]),
+    ("mirt_scene_layout", C.c_int64, [P, I, P, I, I, P, C.c_size_t, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),

@@ -1471,299 +1471,6 @@ int ensure(void** p, size_t* cap, size_t bytes)
     return MIRT_OK;
 }
 
-// The pruning bound (trace.h Prune) holds for a tree in which every leaf box
-// holds its sphere's box as bvh.c:26-46 computes it, fl(c -+ r), and every
-// inner box holds both children's boxes; the reference's own trees are built
-// that way. Also returns the scene constants of the bound. A NaN anywhere,
-// a non-finite sphere or a tree that does not nest turns pruning off.
-// A 0-sphere leaf whose sphere (hit.c:96-97 tests it) is no non-empty leaf's
-// tested sphere: a tree built over part of an array (benchmark.c:317 builds
-// over [0, n - 1)) whose SAH fallback left a last leaf empty points at the
-// element after the range, which only that leaf tests. The pruned and
-// ordered walks drop 0-sphere leaves (dead_leaf), so such a tree is walked
-// in the reference's DFS order instead.
-bool orphan_phantoms(const mirt_node* nd, int nn, int ns)
-{
-    std::vector<char> tested((size_t)ns + 1, 0);
-    for (int i = 0; i < nn; i++)
-        if (nd[i].sphere >= 0 && nd[i].sphere < ns && !(nd[i].skip & MIRT_NODE_EMPTY)) tested[nd[i].sphere] = 1;
-    for (int i = 0; i < nn; i++)
-        if (nd[i].sphere >= 0 && nd[i].sphere < ns && (nd[i].skip & MIRT_NODE_EMPTY) && !tested[nd[i].sphere])
-            return true;
-    return false;
-}
-
-bool tree_encloses(const mirt_sphere* sp, int ns, const mirt_node* nd, int nn, float* r_max, float* c_max)
-{
-    float rm = 0.0f, cm = 0.0f;
-    for (int i = 0; i < ns; i++) {
-        const float c[3] = {sp[i].center.x, sp[i].center.y, sp[i].center.z};
-        const float r = std::fabs(sp[i].radius);
-        if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || !std::isfinite(r)) return false;
-        rm = std::max(rm, r);
-        cm = std::max(cm, std::max(std::fabs(c[0]), std::max(std::fabs(c[1]), std::fabs(c[2]))) + r);
-    }
-    auto holds = [](const mirt_node& outer, const mirt_node& inner) {
-        if (inner.skip & MIRT_NODE_EMPTY) return true;  // +inf/-inf box, no sphere
-        for (int k = 0; k < 3; k++)
-            if (!(outer.bmin[k] <= inner.bmin[k] && outer.bmax[k] >= inner.bmax[k])) return false;
-        return true;
-    };
-    for (int i = 0; i < nn; i++) {
-        const mirt_node& n = nd[i];
-        if (n.skip & MIRT_NODE_EMPTY) continue;
-        if (n.sphere >= 0) {
-            if (n.sphere >= ns) continue;  // the never-hit sentinel
-            const mirt_sphere& s = sp[n.sphere];
-            const float c[3] = {s.center.x, s.center.y, s.center.z};
-            const float r = std::fabs(s.radius);
-            for (int k = 0; k < 3; k++)
-                if (!(n.bmin[k] <= c[k] - r && n.bmax[k] >= c[k] + r)) return false;
-        } else {
-            const uint32_t left = (uint32_t)i + 1, right = nd[left].skip & MIRT_SKIP_MASK;
-            if (!holds(n, nd[left]) || (right < (uint32_t)nn && right < (n.skip & MIRT_SKIP_MASK) && !holds(n, nd[right])))
-                return false;
-        }
-    }
-    *r_max = rm;
-    *c_max = cm;
-    return true;
-}
-
-// A leaf the fast walks may drop: the &spheres[N] sentinel (never hits), or
-// a 0-sphere leaf. hit.c:96-97 does test a 0-sphere leaf's sphere (its box,
-// create_empty_aabb's, always passes): spheres[start] of its range when the
-// SAH fallback split left it empty (mid == start: the first sphere of its
-// sibling's range), spheres[end] when it split right (mid == end: a sphere
-// of some LATER subtree). Dropping it is exact when that sphere is the
-// tested sphere of a non-empty leaf (upload checks this, `orphan_phantoms`;
-// otherwise only the reference-order DFS walk runs) and the ray reaches that
-// leaf whenever it hits the sphere: the leaf's box holds the sphere's box
-// fl(c -+ r) (checked, tree_encloses), the reference slab test is monotone
-// under containment, so this rests on ONE assumption -- hit.c:49-82's
-// division slab test passes the box fl(c -+ r) of every sphere that
-// hit.c:19-39 reports hit. Both are exact-rounding computations of the same
-// chord; tests/test_gpu_parity.py test_phantom_grazing_rays aims grazing rays
-// at the spheres of both kinds of 0-sphere leaf and compares the fast walks
-// with the DFS walk and the oracle.
-bool dead_leaf(const mirt_node* nd, uint32_t i, int ns)
-{
-    return nd[i].sphere >= 0 && ((nd[i].skip & MIRT_NODE_EMPTY) || nd[i].sphere >= ns);
-}
-
-// The node a walk may take in place of flat node ci: an inner node one of
-// whose children is dead adds nothing but its box test, which its live
-// child's (nested, hence stricter) box test implies -- so the chains of
-// one-sided splits the reference's SAH fallback builds (bvh.c:139-141,
-// runs of nodes each with a 0-sphere leaf beside the rest of the range)
-// collapse to the subtree that can hit. kPNone: nothing below can hit.
-uint32_t live_node(const mirt_node* nd, uint32_t ci, int ns)
-{
-    for (;;) {
-        if (nd[ci].sphere >= 0) return dead_leaf(nd, ci, ns) ? kPNone : ci;
-        const uint32_t l = ci + 1, r = nd[ci + 1].skip & MIRT_SKIP_MASK;
-        const bool dl = dead_leaf(nd, l, ns), dr = dead_leaf(nd, r, ns);
-        if (dl && dr) return kPNone;
-        if (!dl && !dr) return ci;
-        ci = dl ? r : l;
-    }
-}
-
-// PNode layout (trace.h) of a validated flat tree. Returns whether ordered
-// walks may use it: hit-able leaves must carry strictly increasing sphere
-// indices in DFS order (then the index is hit.c:108's tie key -- true of the
-// reference's trees, whose build partitions the array in place) and the
-// inner depth must leave the packet walk's stack (one entry per level)
-// within 64.
-// grow > 0: an inner child's box grown by `grow` on each face (rounded
-// outward): the camera packets' margin-free test (trace.h); leaf children keep
-// their exact boxes, which gate every sphere.
-bool build_pnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, std::vector<PNode>& pn, double grow)
-{
-    std::vector<uint32_t> pidx((size_t)nn, kPNone);
-    uint32_t np = 1;
-    for (int i = 0; i < nn; i++)
-        if (nd[i].sphere < 0) pidx[i] = np++;
-    pn.assign(np, PNode{});
-    auto set_child = [&](PNode& p, int k, uint32_t c) {
-        const uint32_t ci = live_node(nd, c, ns);
-        if (ci == kPNone) {  // nothing below can hit: an empty slot
-            float* slot = k ? p.c1 : p.c0;
-            std::memcpy(slot, nd[c].bmin, sizeof nd[c].bmin);
-            std::memcpy(slot + 3, nd[c].bmax, sizeof nd[c].bmax);
-            (k ? p.ref1 : p.ref0) = kPNone;
-            return;
-        }
-        const mirt_node& n = nd[ci];
-        float* slot = k ? p.c1 : p.c0;
-        uint32_t ref = pidx[ci];
-        std::memcpy(slot, n.bmin, sizeof n.bmin);
-        std::memcpy(slot + 3, n.bmax, sizeof n.bmax);
-        if (n.skip & MIRT_NODE_EMPTY) {
-            ref = kPNone;  // a 0-sphere leaf: passes, never hits
-        } else if (n.sphere >= 0) {
-            if (n.sphere >= ns || (uint32_t)n.sphere > kPIndex) {
-                ref = kPNone;
-            } else {
-                ref = kPLeaf | (uint32_t)n.sphere;
-            }
-        }
-        if (grow > 0.0 && ref != kPNone && !(ref & kPLeaf))
-            for (int a = 0; a < 3; a++) {
-                slot[a] = std::nextafter((float)((double)slot[a] - grow), -INFINITY);
-                slot[3 + a] = std::nextafter((float)((double)slot[3 + a] + grow), INFINITY);
-            }
-        (k ? p.ref1 : p.ref0) = ref;
-    };
-    pn[0].ref0 = pn[0].ref1 = kPNone;
-    pn[0].flat = 0xffffffffu;  // flat + 1 == 0: the whole tree
-    pn[0].end = (uint32_t)nn;
-    if (nn > 0) set_child(pn[0], 0, 0);
-    bool mono = nn > 0;
-    int last = -1;
-    std::vector<uint32_t> ends;  // subtree ends of the open inner nodes
-    size_t depth = 0;
-    for (int i = 0; i < nn; i++) {
-        while (!ends.empty() && ends.back() <= (uint32_t)i) ends.pop_back();
-        if (nd[i].sphere < 0) {
-            PNode& p = pn[pidx[i]];
-            set_child(p, 0, (uint32_t)i + 1);
-            set_child(p, 1, nd[i + 1].skip & MIRT_SKIP_MASK);
-            p.flat = (uint32_t)i;
-            p.end = nd[i].skip & MIRT_SKIP_MASK;
-            ends.push_back(nd[i].skip & MIRT_SKIP_MASK);
-            depth = std::max(depth, ends.size());
-        } else if (!(nd[i].skip & MIRT_NODE_EMPTY) && nd[i].sphere < ns) {
-            if (nd[i].sphere <= last) mono = false;
-            last = nd[i].sphere;
-        }
-    }
-    return mono && depth + 2 <= 64;
-}
-
-// fp16 bits of the largest half <= v / the smallest half >= v (a value
-// beyond the fp16 range rounds out to -inf / +inf: still a superset).
-uint16_t half_bits(float v)
-{
-    const _Float16 h = (_Float16)v;
-    uint16_t b;
-    std::memcpy(&b, &h, 2);
-    return b;
-}
-float half_value(uint16_t b)
-{
-    _Float16 h;
-    std::memcpy(&h, &b, 2);
-    return (float)h;
-}
-uint16_t half_down(float v)
-{
-    uint16_t b = half_bits(v);
-    while (half_value(b) > v) b = b == 0x0000 ? 0x8001 : (b & 0x8000) ? b + 1 : b - 1;
-    return b;
-}
-uint16_t half_up(float v)
-{
-    uint16_t b = half_bits(v);
-    while (half_value(b) < v) b = b == 0x8000 ? 0x0001 : (b & 0x8000) ? b - 1 : b + 1;
-    return b;
-}
-
-// HNode layout (trace.h) of a validated flat tree: HNode 0 holds the root;
-// an HNode for each inner node that is some HNode's slot holds that node's
-// grandchildren (a leaf child standing in for its own); one leaf (sphere +
-// exact box) per leaf slot. Used only when the PNode conditions hold and the boxes nest.
-// grow > 0 (the bounce walks' bounded slab test): every slot box grown by `grow` on each face
-// before the outward fp16 rounding.
-void build_hnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, std::vector<HNode>& hn,
-                  std::vector<HAux>& aux, std::vector<float4>& lgeo, std::vector<LeafBox>& lbox, double grow)
-{
-    hn.assign(1, HNode{});
-    aux.assign(1, HAux{0xffffffffu, (uint32_t)nn});  // flat + 1 == 0: the whole tree
-    lgeo.clear();
-    lbox.clear();
-    std::vector<uint32_t> todo;  // inner nodes waiting for their HNode: HNode 1 + i is todo[i]
-    auto fill = [&](size_t hi, int k, uint32_t c) {
-        HNode& h = hn[hi];
-        const uint32_t ci = live_node(nd, c, ns);
-        if (ci == kPNone) {
-            h.slot[k].ref = kPNone;
-            return;
-        }
-        const mirt_node& n = nd[ci];
-        for (int a = 0; a < 3; a++) {
-            float lo = n.bmin[a], hi = n.bmax[a];
-            if (grow > 0.0) {   // rounded outward again: the float of lo - grow may lie above it
-                lo = std::nextafter((float)((double)lo - grow), -INFINITY);
-                hi = std::nextafter((float)((double)hi + grow), INFINITY);
-            }
-            h.slot[k].box[a] = (uint32_t)half_down(lo) | ((uint32_t)half_up(hi) << 16);
-        }
-        uint32_t ref;
-        if (n.skip & MIRT_NODE_EMPTY) {
-            ref = kPNone;
-        } else if (n.sphere >= 0) {
-            if (n.sphere >= ns) {
-                ref = kPNone;
-            } else {
-                LeafBox l{};
-                std::memcpy(l.lo, n.bmin, sizeof l.lo);
-                std::memcpy(l.hi, n.bmax, sizeof l.hi);
-                l.sphere = n.sphere;
-                const mirt_sphere& s = sp[n.sphere];
-                ref = kPLeaf | (uint32_t)lbox.size();
-                lbox.push_back(l);
-                lgeo.push_back(make_float4(s.center.x, s.center.y, s.center.z, s.radius));
-            }
-        } else {
-            todo.push_back(ci);
-            ref = (uint32_t)todo.size();
-        }
-        h.slot[k].ref = ref;
-    };
-    for (int k = 0; k < 4; k++) hn[0].slot[k].ref = kPNone;
-    if (nn == 0) return;
-    fill(0, 0, 0);
-    for (size_t next = 0; next < todo.size(); next++) {
-        const uint32_t y = todo[next];
-        HNode h{};
-        for (int k = 0; k < 4; k++) h.slot[k].ref = kPNone;
-        hn.push_back(h);
-        aux.push_back(HAux{y, nd[y].skip & MIRT_SKIP_MASK});
-        // the four slots: y's live children, then the inner slot with the
-        // largest box replaced by its two live children while a slot is
-        // free (every slot stays inside y's flat subtree, which HAux walks)
-        uint32_t cut[4];
-        int m = 0;
-        auto add = [&](uint32_t c) {
-            const uint32_t ci = live_node(nd, c, ns);
-            if (ci != kPNone) cut[m++] = ci;
-        };
-        add(y + 1);
-        add(nd[y + 1].skip & MIRT_SKIP_MASK);
-        while (m < 4) {
-            int best = -1;
-            float best_area = -1.0f;
-            for (int j = 0; j < m; j++) {
-                const mirt_node& n = nd[cut[j]];
-                if (n.sphere >= 0) continue;
-                const float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-                const float area = dx * dy + dy * dz + dz * dx;
-                if (area > best_area || best < 0) {
-                    best = j;
-                    best_area = area;
-                }
-            }
-            if (best < 0) break;
-            const uint32_t c = cut[best];
-            cut[best] = cut[--m];
-            add(c + 1);
-            add(nd[c + 1].skip & MIRT_SKIP_MASK);
-        }
-        for (int k = 0; k < m; k++) fill(hn.size() - 1, k, cut[k]);
-    }
-}
-
 // MIRT_OPT_LEAF_BATCH: the bounce walk loads a step's passing leaf spheres
 // together (bounce_kernel WALK 4) -- by default when the four-wide tree is
 // larger than the chip's L2 (32 MiB over the 8 XCDs), where the leaf loads
@@ -2217,105 +1924,56 @@ try {
     // a malformed tree must not send the host layout builders or the kernels
     // out of bounds
     if (int rc = validate_flat(nodes, nn, ns, 0, "mirt_scene_upload_flat")) return rc;
-    float r_max = 0.0f, c_max = 0.0f;
-    const bool encloses = tree_encloses(spheres, ns, nodes, nn, &r_max, &c_max) && !orphan_phantoms(nodes, nn, ns);
-    std::vector<float4> geo((size_t)ns + 1);
-    std::vector<uint32_t> col((size_t)ns + 1);
-    for (int i = 0; i < ns; i++) {
-        geo[i] = make_float4(spheres[i].center.x, spheres[i].center.y, spheres[i].center.z, spheres[i].radius);
-        std::memcpy(&col[i], &spheres[i].color, 4);
-    }
-    geo[ns] = make_float4(NAN, NAN, NAN, NAN);  // &spheres[N] sentinel: never hits
-    col[ns] = 0xff000000u;
-    for (void* p : {(void*)c->d_nodes, (void*)c->d_nodes32, (void*)c->d_geo, (void*)c->d_color, (void*)c->d_pnodes,
-                    (void*)c->d_hnodes, (void*)c->d_haux, (void*)c->d_leaves, (void*)c->d_ndepth})
-        if (p) (void)hipFree(p);
-    c->d_ndepth = nullptr;
-    c->d_pnodes = nullptr;
-    c->d_hnodes = nullptr;
-    c->d_haux = nullptr;
-    c->d_leaves = nullptr;
-    c->d_nodes = nullptr;
-    c->d_nodes32 = nullptr;
-    c->d_geo = nullptr;
-    c->d_color = nullptr;
-    c->num_spheres = -1;
-    // device layout: 64-B nodes with each leaf's sphere inline (trace.h DNode)
-    std::vector<DNode> dn((size_t)nn);
-    for (int i = 0; i < nn; i++) {
-        DNode& d = dn[i];
-        std::memset(&d, 0, sizeof d);
-        std::memcpy(d.bmin, nodes[i].bmin, sizeof d.bmin);
-        std::memcpy(d.bmax, nodes[i].bmax, sizeof d.bmax);
-        d.sphere = nodes[i].sphere;
-        d.skip = nodes[i].skip;
-        d.geo = nodes[i].sphere >= 0 ? geo[nodes[i].sphere] : geo[ns];
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_nodes, sizeof(DNode) * (size_t)(nn > 0 ? nn : 1)));
-    HIP_TRY(hipMalloc((void**)&c->d_geo, sizeof(float4) * geo.size()));
-    HIP_TRY(hipMalloc((void**)&c->d_color, sizeof(uint32_t) * col.size()));
-    HIP_TRY(hipMalloc((void**)&c->d_nodes32, sizeof(mirt_node) * (size_t)(nn > 0 ? nn : 1)));
-    if (nn > 0) HIP_TRY(hipMemcpy(c->d_nodes, dn.data(), sizeof(DNode) * (size_t)nn, hipMemcpyHostToDevice));
-    if (nn > 0) HIP_TRY(hipMemcpy(c->d_nodes32, nodes, sizeof(mirt_node) * (size_t)nn, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_geo, geo.data(), sizeof(float4) * geo.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_color, col.data(), sizeof(uint32_t) * col.size(), hipMemcpyHostToDevice));
-    // the margin-free box tests (bounce walks, camera packets): C bounds every box coordinate and every sphere point
-    // (so every bounce-ray origin, up to rounding: the margin 2^-10 C + 2^-10),
-    // and the slot boxes grow by 2^-19 C (trace.h slab_cons_fast<BND>)
-    double cb = c_max;
-    for (int i = 0; i < nn; i++) {
-        if (nodes[i].skip & MIRT_NODE_EMPTY) continue;
-        for (int a = 0; a < 3; a++)
-            for (float v : {nodes[i].bmin[a], nodes[i].bmax[a]})
-                if (std::isfinite(v)) cb = std::max(cb, (double)std::fabs(v));
-    }
-    cb = cb * (1.0 + 0x1p-10) + 0x1p-10;
-    const bool bounded = encloses && cb < 6.0e4;   // fp16 range: the grown boxes stay finite
-    c->o_bound = bounded ? (float)cb : 0.0f;   // 0: every bounce ray takes the exact test
-    std::vector<PNode> pn;
-    const bool ordered = build_pnodes(nodes, nn, spheres, ns, pn, bounded ? cb * 0x1p-19 : 0.0);
-    HIP_TRY(hipMalloc((void**)&c->d_pnodes, sizeof(PNode) * pn.size()));
-    HIP_TRY(hipMemcpy(c->d_pnodes, pn.data(), sizeof(PNode) * pn.size(), hipMemcpyHostToDevice));
-    std::vector<HNode> hn;
-    std::vector<HAux> hx;
-    std::vector<float4> lgeo;
-    std::vector<LeafBox> lbox;
-    build_hnodes(nodes, nn, spheres, ns, hn, hx, lgeo, lbox, bounded ? cb * 0x1p-19 : 0.0);
-    const size_t nl = lbox.size();
-    const size_t box_off = (sizeof(float4) * nl + 255) & ~(size_t)255;
-    HIP_TRY(hipMalloc((void**)&c->d_hnodes, sizeof(HNode) * hn.size()));
-    HIP_TRY(hipMalloc((void**)&c->d_haux, sizeof(HAux) * hx.size()));
-    HIP_TRY(hipMalloc((void**)&c->d_leaves, box_off + sizeof(LeafBox) * std::max<size_t>(nl, 1)));
-    HIP_TRY(hipMemcpy(c->d_hnodes, hn.data(), sizeof(HNode) * hn.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_haux, hx.data(), sizeof(HAux) * hx.size(), hipMemcpyHostToDevice));
-    if (nl) {
-        HIP_TRY(hipMemcpy(c->d_leaves, lgeo.data(), sizeof(float4) * nl, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_leaves + box_off, lbox.data(), sizeof(LeafBox) * nl, hipMemcpyHostToDevice));
-    }
-    // node depths (pre-order: the children of inner node i are i + 1 and the
-    // left subtree's skip), clamped to 255 -- the overlay's colour key
-    std::vector<uint8_t> ndepth((size_t)std::max(nn, 1), 0);
-    for (int i = 0; i < nn; i++) {
-        if (nodes[i].sphere >= 0) continue;
-        const uint8_t d = ndepth[i] == 255 ? 255 : (uint8_t)(ndepth[i] + 1);
-        ndepth[i + 1] = d;
-        ndepth[nodes[i + 1].skip & MIRT_SKIP_MASK] = d;
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_ndepth, ndepth.size()));
-    HIP_TRY(hipMemcpy(c->d_ndepth, ndepth.data(), ndepth.size(), hipMemcpyHostToDevice));
+    SceneLayout lay;
+    build_scene_layout(spheres, ns, nodes, nn, lay);
+    // the device arrays: `alloc` bytes allocated at *dst (0: the array goes
+    // `off` bytes into the allocation the row before made), `bytes` copied
+    const size_t n1 = nn > 0 ? nn : 1, nl = lay.leaf_box.size();
+    const struct {
+        void** dst;
+        size_t alloc, off;
+        const void* src;
+        size_t bytes;
+    } up[] = {
+        {(void**)&c->d_nodes, sizeof(DNode) * n1, 0, lay.dnodes.data(), sizeof(DNode) * (size_t)nn},
+        {(void**)&c->d_nodes32, sizeof(mirt_node) * n1, 0, nodes, sizeof(mirt_node) * (size_t)nn},
+        {(void**)&c->d_geo, sizeof(float4) * lay.geo.size(), 0, lay.geo.data(), sizeof(float4) * lay.geo.size()},
+        {(void**)&c->d_color, sizeof(uint32_t) * lay.color.size(), 0, lay.color.data(),
+         sizeof(uint32_t) * lay.color.size()},
+        {(void**)&c->d_pnodes, sizeof(PNode) * lay.pnodes.size(), 0, lay.pnodes.data(),
+         sizeof(PNode) * lay.pnodes.size()},
+        {(void**)&c->d_hnodes, sizeof(HNode) * lay.hnodes.size(), 0, lay.hnodes.data(),
+         sizeof(HNode) * lay.hnodes.size()},
+        {(void**)&c->d_haux, sizeof(HAux) * lay.haux.size(), 0, lay.haux.data(), sizeof(HAux) * lay.haux.size()},
+        {(void**)&c->d_leaves, lay.leaf_box_off + sizeof(LeafBox) * std::max<size_t>(nl, 1), 0, lay.leaf_geo.data(),
+         sizeof(float4) * nl},
+        {(void**)&c->d_leaves, 0, lay.leaf_box_off, lay.leaf_box.data(), sizeof(LeafBox) * nl},
+        {(void**)&c->d_ndepth, lay.ndepth.size(), 0, lay.ndepth.data(), lay.ndepth.size()},
+    };
+    for (const auto& u : up)
+        if (u.alloc) {
+            if (*u.dst) (void)hipFree(*u.dst);
+            *u.dst = nullptr;
+        }
+    c->num_spheres = -1;  // until every array is in place ctx_ok rejects the context
+    auto put = [](void** dst, size_t alloc, size_t off, const void* src, size_t bytes) {
+        if (alloc) HIP_TRY(hipMalloc(dst, alloc));
+        if (bytes) HIP_TRY(hipMemcpy((char*)*dst + off, src, bytes, hipMemcpyHostToDevice));
+        return (int)MIRT_OK;
+    };
+    for (const auto& u : up)
+        if (int rc = put(u.dst, u.alloc, u.off, u.src, u.bytes)) return rc;
     c->num_nodes = nn;
     c->num_spheres = ns;
-    c->num_hnodes = (uint32_t)hn.size();
-    c->leaf_box_off = box_off;
-    c->leaf_big = sizeof(HNode) * hn.size() + (sizeof(float4) + sizeof(LeafBox)) * nl > ((size_t)32 << 20);
-    {
-        const uint32_t r = hn[0].slot[0].ref;
-        c->wide_root = (r != kPNone && !(r & kPLeaf)) ? r : 0u;
-    }
-    c->ordered_ok = ordered;
-    c->prune_ok = encloses;
-    c->r_max = r_max;
-    c->c_max = c_max;
+    c->num_hnodes = (uint32_t)lay.hnodes.size();
+    c->leaf_box_off = lay.leaf_box_off;
+    c->leaf_big = lay.leaf_big;
+    c->wide_root = lay.wide_root;
+    c->ordered_ok = lay.ordered;
+    c->prune_ok = lay.encloses;
+    c->r_max = lay.r_max;
+    c->c_max = lay.c_max;
+    c->o_bound = lay.o_bound;
     return MIRT_OK;
 } catch (const std::bad_alloc&) {
     set_error("mirt_scene_upload_flat: out of host memory");

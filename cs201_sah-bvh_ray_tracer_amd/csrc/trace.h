@@ -14,88 +14,13 @@
 #include <cstdint>
 
 #include "../../include/mirt.h"
+#include "layout.h"
 #include "rng.h"
 
 namespace mirt {
 
 constexpr float kEps = 0.000001f;  // constants.h:6
 constexpr int kMaxDepth = 8;       // bounce levels kept in registers
-
-// Device copy of a flattened node (mirt_node, include/mirt.h) padded to 64 B,
-// with the leaf's sphere (centre, radius) inline so a leaf step needs no
-// second, dependent load. Inner nodes and the &spheres[N] sentinel carry NaN
-// geometry (never hits).
-struct __attribute__((aligned(64))) DNode {
-    float bmin[3];
-    float bmax[3];
-    int32_t sphere;   // leaf: sphere index; inner: -1
-    uint32_t skip;    // next node after this subtree | MIRT_NODE_EMPTY
-    float4 geo;       // leaf sphere centre.xyz, radius
-    uint32_t pad[4];
-};
-static_assert(sizeof(DNode) == 64, "device node is 64 B");
-
-// The same tree re-laid for ordered walks: one node per inner node of the
-// reference tree holding BOTH children, so one load tests both and the walk
-// can enter the nearer child first. PNode 0 is a virtual parent whose only
-// child is the root. A child reference is an inner PNode index, kPLeaf |
-// sphere index (a leaf that can hit), or kPNone (no child that can ever hit:
-// a 0-sphere leaf or the &spheres[N] sentinel of hit.c). A child slot holds
-// the child's box (lo.xyz, hi.xyz) -- for a leaf that is the box of the
-// node's whole sphere range, not of its one sphere (a depth-40 leaf keeps
-// the range's bounds but tests only node->sphere, bvh.c:122-136), so the
-// sphere itself is fetched when the box passes.
-// `flat` and `end` locate the node in the flat pre-order tree, [flat + 1,
-// end) being its children's subtrees, which a walk can take in DFS order
-// without a stack.
-constexpr uint32_t kPLeaf = 0x80000000u;
-constexpr uint32_t kPNone = 0xffffffffu;
-constexpr uint32_t kPIndex = 0x7fffffffu;
-struct __attribute__((aligned(64))) PNode {
-    float c0[6];
-    float c1[6];
-    uint32_t ref0, ref1;
-    uint32_t flat, end;
-};
-static_assert(sizeof(PNode) == 64, "ordered node is 64 B");
-
-// Four-wide layout for per-lane walks: HNode(Y), for an inner node Y of the
-// reference tree, holds Y's grandchildren (a child that is a leaf stands in
-// for its own slot), so a walk takes half the dependent steps. The skipped
-// children's boxes need no test: the tree's boxes nest (checked at upload)
-// and hit.c's slab test is monotone under containment (correctly rounded
-// subtraction and division are monotone, so a box inside another gets a
-// later entry and an earlier exit), so a ray that passes a box passes every
-// enclosing one -- the leaves reached are exactly those hit.c:91-109
-// reaches. The same argument lets slot boxes be CONSERVATIVE: each is
-// stored in fp16 rounded outward (a superset) and tested with a fast test
-// that passes when undecided -- entering an inner node too eagerly costs
-// work, never a result, because every leaf is still gated by its exact box.
-// A leaf slot's sphere and its exact box live in two arrays (structure of
-// arrays, round 6): the gate reads the 16-B sphere first and the 32-B box only
-// for a hit that could win, so the spheres the walks read are packed eight to
-// a 128-B line (a 48-B record per leaf held 2.7) and the hot part of a large
-// tree -- HNodes + spheres -- is two thirds of the bytes it was. 64 B per node = the bytes of two fp32 boxes: divergent
-// per-lane loads are bound by the bytes the texture path returns.
-// HNode 0 is a virtual node whose only slot is the root; slot references: an
-// inner HNode index, kPLeaf | leaf index, or kPNone. HAux holds the
-// node's flat DFS segment [flat + 1, end), read only when the stack is full.
-struct __attribute__((aligned(64))) HNode {
-    struct Slot {
-        uint32_t box[3];  // per axis: fp16 lo (bits 0-15) | fp16 hi (bits 16-31)
-        uint32_t ref;
-    } slot[4];            // 16 B per slot: one dwordx4 each
-};
-static_assert(sizeof(HNode) == 64, "wide node is 64 B");
-struct HAux {
-    uint32_t flat, end;
-};
-struct __attribute__((aligned(32))) LeafBox {
-    float lo[3], hi[3];  // the leaf's exact box (bvh.c bounds)
-    int32_t sphere;
-    uint32_t pad;
-};
-static_assert(sizeof(LeafBox) == 32, "leaf box is 32 B");
 
 // Read-only scene in HBM (L2 / Infinity-Cache resident at the BASELINE sizes).
 struct DevScene {

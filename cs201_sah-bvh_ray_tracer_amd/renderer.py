@@ -113,6 +113,31 @@ def validate_bvh(nodes, num_spheres):
           "mirt_bvh_validate_flat")
 
 
+def scene_layout(spheres, tree=None):
+    """mirt_scene_layout: the device layouts an upload of `spheres` with `tree`
+    (a Bvh, an abi.NODE array or None) would send, computed on the host -- no
+    Renderer, no GPU. Returns (info, parts): info the mirt_scene_layout_info
+    fields as a dict, parts one numpy array per abi.LAYOUT_PARTS name."""
+    spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+    nodes = np.zeros(0, abi.NODE) if tree is None else tree.nodes if isinstance(tree, Bvh) else tree
+    nodes = np.ascontiguousarray(nodes, abi.NODE)
+    L = load()
+    raw = abi.SceneLayoutInfo()
+    args = (ptr(spheres) if len(spheres) else None, len(spheres), ptr(nodes) if len(nodes) else None, len(nodes))
+    check(L.mirt_scene_layout(*args, 0, None, 0, C.byref(raw)), "mirt_scene_layout")
+    count = dict(dnodes=len(nodes), geo=len(spheres) + 1, color=len(spheres) + 1, pnodes=raw.num_pnodes,
+                 hnodes=raw.num_hnodes, haux=raw.num_hnodes, leaf_geo=raw.num_leaves, leaf_box=raw.num_leaves,
+                 ndepth=max(len(nodes), 1))
+    parts = {}
+    for part, (name, dtype) in enumerate(abi.LAYOUT_PARTS):
+        out = np.zeros(count[name], dtype)
+        size = check(L.mirt_scene_layout(*args, part, ptr(out), out.nbytes, None), "mirt_scene_layout")
+        if size != out.nbytes:
+            raise MirtError(f"mirt_scene_layout: part {name} is {size} bytes, expected {out.nbytes}")
+        parts[name] = out
+    return {name: getattr(raw, name) for name, _ in raw._fields_}, parts
+
+
 def build_bvh_cached(path, spheres, start=0, end=None, depth=0):
     """build_bvh through a flattened-tree cache file (mirt_bvh_build_flat_cached):
     returns (Bvh, cached) with cached 1 = loaded from `path`, 0 = built and

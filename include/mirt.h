@@ -17,7 +17,8 @@
  * Diagnostic surface (for the test suite; may change between releases):
  * mirt_box_form_pairs and mirt_sphere_form_pairs run the walks' filtered box
  * and sphere tests on caller-given pairs; mirt_build_partition_probe runs the
- * device build's partition on caller-given keys.
+ * device build's partition on caller-given keys; mirt_scene_layout returns
+ * the device layouts an upload derives from a scene, computed on the host.
  */
 #ifndef MIRT_H
 #define MIRT_H
@@ -381,6 +382,25 @@ int mirt_sphere_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_spher
    (j itself outside the segments). */
 int mirt_build_partition_probe(mirt_ctx *ctx, const float *centre, int n, const int32_t *seg, int nseg,
                                const float *split, int32_t *perm);
+/* The device layouts mirt_scene_upload_flat derives from a scene, computed on
+   the host alone (csrc/scene_layout.cpp; needs no ctx and makes no HIP call):
+   the tree is checked as the upload checks it (MIRT_E_INVALID), then `part`
+   is exactly the bytes the upload would send for that array (csrc/layout.h
+   has the structs). Returns the part's size in bytes, or a negative error;
+   copies the part when out != NULL and cap >= size; info may be NULL. */
+typedef struct mirt_scene_layout_info {
+    int32_t  encloses, ordered, leaf_big;   /* boxes nest (pruning allowed) / ordered walks allowed /
+                                               four-wide layout larger than the chip's L2 */
+    float    r_max, c_max, o_bound;         /* largest radius, largest |centre|_inf + radius, the bounded
+                                               slab tests' coordinate bound C (0: none) */
+    uint32_t num_pnodes, num_hnodes, num_leaves, wide_root;
+    uint64_t leaf_box_off;                  /* byte offset of the leaf boxes behind the leaf spheres */
+} mirt_scene_layout_info;
+enum { MIRT_LAYOUT_DNODES = 0, MIRT_LAYOUT_GEO = 1, MIRT_LAYOUT_COLOR = 2, MIRT_LAYOUT_PNODES = 3,
+       MIRT_LAYOUT_HNODES = 4, MIRT_LAYOUT_HAUX = 5, MIRT_LAYOUT_LEAF_GEO = 6, MIRT_LAYOUT_LEAF_BOX = 7,
+       MIRT_LAYOUT_NDEPTH = 8 };
+int64_t mirt_scene_layout(const mirt_sphere *spheres, int num_spheres, const mirt_node *nodes, int num_nodes,
+                          int part, void *out, size_t cap, mirt_scene_layout_info *info);
 
 /* The camera ray of every pixel of the shard (ray.c:17-32 with the pixel
    mapping of main.c:356-365). */

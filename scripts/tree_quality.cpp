@@ -1,6 +1,6 @@
 // CPU study: how many four-wide node visits and leaf gates does a bounce ray
 // of the BASELINE scenes cost on (A) the four-wide tree the library derives
-// from the reference's own tree (render.hip build_hnodes: live_node chain
+// from the reference's own tree (scene_layout.cpp build_hnodes: live_node chain
 // collapse, greedy four-slot cut) against (B) a four-wide tree built afresh
 // over the same live leaves by a binned SAH?
 //

@@ -1,10 +1,11 @@
-// Host half of libmirt (csrc/host_scene.cpp, bvh_build.cpp, bvh_cache.cpp)
-// under the sanitizers: `make -C cs201_sah-bvh_ray_tracer_amd/csrc san`
+// Host half of libmirt (csrc/host_scene.cpp, bvh_build.cpp, bvh_cache.cpp,
+// scene_layout.cpp) under the sanitizers: `make -C cs201_sah-bvh_ray_tracer_amd/csrc san`
 // links this driver with those sources built -fsanitize=address,undefined
 // (build/san_asan) and -fsanitize=thread (build/san_tsan). It exercises the
 // threaded build (subtrees forked above 32k spheres), the pointer-tree build
-// and flatten, tree validation on malformed input, and the tree cache file
-// on good, corrupt, truncated and unwritable paths. Exit 0 = every check held
+// and flatten, tree validation on malformed input, the tree cache file
+// on good, corrupt, truncated and unwritable paths, and the scene layout
+// builders (build_scene_layout) on the tree shapes that steer their indexing. Exit 0 = every check held
 // and no sanitizer fired (the sanitizers abort on a finding).
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../../cs201_sah-bvh_ray_tracer_amd/csrc/layout.h"
 #include "../../include/mirt.h"
 
 static int failures = 0;
@@ -50,6 +52,34 @@ static bool same(const std::vector<mirt_node>& a, const std::vector<mirt_node>& 
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(mirt_node)) == 0;
 }
 
+// build_scene_layout on a validated tree: every reference the walks would
+// follow stays inside its array, and the arrays have the sizes the upload
+// copies. Returns the number of 0-sphere leaves (MIRT_NODE_EMPTY).
+static int check_layout(const std::vector<mirt_sphere>& s, int ns, const std::vector<mirt_node>& nd)
+{
+    using namespace mirt;
+    const int nn = (int)nd.size();
+    CHECK(mirt_bvh_validate_flat(nn ? nd.data() : nullptr, nn, ns) == MIRT_OK);
+    SceneLayout lay;
+    build_scene_layout(ns ? s.data() : nullptr, ns, nn ? nd.data() : nullptr, nn, lay);
+    CHECK(lay.dnodes.size() == (size_t)nn && lay.geo.size() == (size_t)ns + 1 && lay.color.size() == (size_t)ns + 1);
+    CHECK(lay.ndepth.size() == (size_t)(nn > 0 ? nn : 1));
+    CHECK(lay.haux.size() == lay.hnodes.size() && lay.leaf_geo.size() == lay.leaf_box.size());
+    CHECK(!lay.pnodes.empty() && !lay.hnodes.empty() && lay.wide_root < lay.hnodes.size());
+    CHECK(lay.leaf_box_off % 256 == 0 && lay.leaf_box_off >= sizeof(Geo4) * lay.leaf_geo.size());
+    for (const PNode& p : lay.pnodes)
+        for (uint32_t ref : {p.ref0, p.ref1})
+            CHECK(ref == kPNone || ((ref & kPLeaf) ? (ref & kPIndex) < (uint32_t)ns : ref < lay.pnodes.size()));
+    for (const HNode& h : lay.hnodes)
+        for (const HNode::Slot& sl : h.slot)
+            CHECK(sl.ref == kPNone ||
+                  ((sl.ref & kPLeaf) ? (sl.ref & kPIndex) < lay.leaf_box.size() : sl.ref < lay.hnodes.size()));
+    for (const LeafBox& l : lay.leaf_box) CHECK(l.sphere >= 0 && l.sphere < ns);
+    int empty = 0;
+    for (const mirt_node& n : nd) empty += (n.skip & MIRT_NODE_EMPTY) != 0;
+    return empty;
+}
+
 int main(int argc, char** argv)
 {
     const std::string dir = argc > 1 ? argv[1] : "/tmp";
@@ -70,6 +100,48 @@ int main(int argc, char** argv)
         CHECK(std::memcmp(s1.data(), s2.data(), s1.size() * sizeof(mirt_sphere)) == 0);
         CHECK(mirt_bvh_validate_flat(f.data(), (int)f.size(), n) == MIRT_OK);
         mirt_free_bvh(root);
+        check_layout(s1, n, f);
+    }
+
+    // a benchmark scene built over [0, n - 1) from depth 20 (benchmark.c:317)
+    // whose last spheres in range coincide: the SAH fallback's trailing
+    // 0-sphere leaves point at spheres[n - 1], past the range -- a real sphere
+    // when the array is declared whole, the never-hit sentinel when not
+    {
+        const int n = 2000, end = n - 1;
+        std::vector<mirt_sphere> s = scene(true, n, 3);
+        for (mirt_sphere& sp : s) sp.center.x -= 1000.0f;  // all x < 0: the fallback leaves its right child empty
+        for (int i = end - 3; i < end; i++) {
+            s[i].center = mirt_vec3{-1.0f, 600.0f, 600.0f};  // beyond the rest on every axis: last in the range
+            s[i].radius = 1.0f;
+        }
+        std::vector<mirt_node> f = flat_build(s, 0, end, 20);
+        int past = 0;
+        for (const mirt_node& nd : f) past += (nd.skip & MIRT_NODE_EMPTY) && nd.sphere == end;
+        CHECK(past > 0);
+        check_layout(s, n, f);
+        check_layout(s, end, f);
+    }
+
+    // scene layouts of the degenerate shapes: no tree, nothing at all, a single
+    // leaf, a small built tree, and coincident spheres (one-sided chains of
+    // 0-sphere leaves down to the depth cap)
+    {
+        std::vector<mirt_sphere> s = scene(false, 5, 1);
+        check_layout(s, 5, {});
+        check_layout({}, 0, {});
+        std::vector<mirt_sphere> one = scene(false, 1, 1);
+        std::vector<mirt_node> f = flat_build(one, 0, 1, 0);
+        CHECK(f.size() == 1);
+        check_layout(one, 1, f);
+        s = scene(false, 1000, 2);
+        f = flat_build(s, 0, 1000, 0);
+        check_layout(s, 1000, f);
+        s = scene(false, 300, 7);
+        for (int k = 0; k < 40; k++)
+            for (int j = 0; j < 6; j++) s.push_back(s[k]);
+        f = flat_build(s, 0, (int)s.size(), 0);
+        CHECK(check_layout(s, (int)s.size(), f) > 100);
     }
 
     // malformed trees are rejected, never walked out of bounds

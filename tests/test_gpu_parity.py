@@ -684,7 +684,7 @@ def test_one_sided_chains_frame(gpu, mirt, oracle):
     fallback: every plane leaves a side empty, so the split lands at x = 0 and
     one child is a 0-sphere leaf -- a chain of one-sided nodes down to the
     depth-40 cap, whose leaf tests only its first sphere. The derived walk
-    layouts skip such chains (render.hip live_node) and fill four-wide nodes
+    layouts skip such chains (scene_layout.cpp live_node) and fill four-wide nodes
     greedily; the frame, per-ray hits and traces must stay the reference's."""
     abi = mirt.abi
     base = mirt.create_random_spheres(3000, 7)
@@ -1007,7 +1007,7 @@ def test_dropin_rebinds_after_free_and_rebuild(mirt, oracle):
 
 
 def test_phantom_grazing_rays(gpu, mirt, oracle):
-    """The fast walks drop 0-sphere leaves (render.hip dead_leaf): exact if a
+    """The fast walks drop 0-sphere leaves (scene_layout.cpp dead_leaf): exact if a
     ray that hits a sphere always passes the box fl(c -+ r) of that sphere's
     own leaf under hit.c:49-82's division test. Rays aimed at the silhouettes
     (within 1e-3 .. 1e-6 of the radius) of the spheres that 0-sphere leaves of

@@ -332,7 +332,7 @@ def test_tree_cache_rejects_forged_files(mirt, small, tmp_path):
 
 def test_sanitizer_builds(tmp_path):
     """The host C++ (threaded build, validation, tree cache file incl. corrupt,
-    truncated and unwritable files) under ASan+UBSan and under TSan
+    truncated and unwritable files, the scene layout builders) under ASan+UBSan and under TSan
     (tests/c/san_host.cpp via `make -C csrc san`): every check holds and no
     sanitizer reports."""
     import subprocess
@@ -352,7 +352,7 @@ def test_phantom_leaves_are_covered(mirt, kind, n, start, end, depth):
     """Every 0-sphere leaf of the BASELINE scenes' trees (and of a
     benchmark.c:317-style build over [0, n - 1) from depth 20) points at a
     sphere some non-empty leaf tests first, or at the never-hit index N: so
-    the upload keeps the fast walks (render.hip orphan_phantoms / dead_leaf)
+    the upload keeps the fast walks (scene_layout.cpp orphan_phantoms / dead_leaf)
     on the trees the bench and the parity tests run."""
     s = mirt.create_random_spheres(n, 1) if kind == "render" else mirt.create_benchmark_spheres(n, 1)
     nd = mirt.build_bvh(s, start, end, depth).nodes
