@@ -109,6 +109,12 @@ class BuildStats(C.Structure):
                 ("device_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class SceneBuildStats(C.Structure):
+    """mirt_scene_build_stats"""
+    _fields_ = [("on_device", C.c_int32), ("levels", C.c_int32), ("nodes", C.c_int32),
+                ("build_ms", C.c_float), ("layout_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 class SceneLayoutInfo(C.Structure):
     """mirt_scene_layout_info"""
     _fields_ = [("encloses", C.c_int32), ("ordered", C.c_int32), ("leaf_big", C.c_int32),
@@ -175,6 +181,10 @@ SIGNATURES = [
     ("mirt_last_build_stats", I, [P, P]),
     ("mirt_build_partition_probe", I, [P, P, I, P, I, P, P]),
     ("mirt_scene_layout", C.c_int64, [P, I, P, I, I, P, C.c_size_t, P]),
+    ("mirt_scene_build_device", I, [P, P, I, I, I, I, P]),
+    ("mirt_scene_upload_flat_device", I, [P, P, I, P, I]),
+    ("mirt_last_scene_build_stats", I, [P, P]),
+    ("mirt_scene_resident_layout", C.c_int64, [P, I, P, C.c_size_t, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),

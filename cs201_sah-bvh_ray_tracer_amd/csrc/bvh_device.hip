@@ -25,7 +25,8 @@
 //              prefix sum over the array, chains are resolved by pointer
 //              doubling, ceil(log2(longest range)) rounds.
 // Then subtree sizes bottom-up, pre-order indices top-down, and the nodes are
-// written in mirt_node layout.
+// written in mirt_node layout. The download of the result is a separate step:
+// mirt_scene_build_device (scene_device.hip) takes the tree where it lies.
 //
 // Order independence needs min/max to be exact and symmetric: a NaN or an
 // infinity among the inputs, or a sphere box coordinate that is -0.0 (fmin(-0,
@@ -733,24 +734,30 @@ int run_partition(BuildState& st, hipStream_t s, int cur, int n, int off, int cn
     return MIRT_OK;
 }
 
-// the build proper; *declined = 1: nothing was changed, the host builder must run
-int device_build(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int sphere0, int depth,
-                 mirt_node** out_nodes, int* out_count, int* declined, int* levels_out)
+// The build proper, left on the device: `total` spheres go to st.aos, the tree
+// of the n of them from `first` on is built (leaf indices count from sphere0)
+// and stays in st.out, *out_count nodes; st.aos then holds all `total` spheres
+// with that range reordered. Enqueued, not waited for: download() or the
+// caller synchronises. *declined = 1: nothing was built, the host builder must run
+int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int total, int first, int n, int sphere0,
+                 int depth, int* out_count, int* declined, int* levels_out)
 {
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
     *declined = 0;
     int rc = ensure_spheres(st, n);
-    if (!rc) rc = ensure(st.aos, (size_t)std::max(n, 1) * sizeof(mirt_sphere));
+    if (!rc) rc = ensure(st.aos, (size_t)std::max(total, 1) * sizeof(mirt_sphere));
     if (!rc) rc = ensure(st.nodes, ((size_t)2 * (size_t)n + 64) * sizeof(BNode));
     if (rc) return rc;
     int* ctl = (int*)st.ctl.p;
     int h_ctl[kCtlWords] = {0, 0, 0, 0};
     int cur = 0;
     HIP_TRY(hipMemsetAsync(ctl, 0, kCtlWords * 4, s));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(st.aos.p, spheres, (size_t)n * sizeof(mirt_sphere), hipMemcpyHostToDevice, s));
+    if (total > 0)
+        HIP_TRY(hipMemcpyAsync(st.aos.p, spheres, (size_t)total * sizeof(mirt_sphere), hipMemcpyHostToDevice, s));
+    uint32_t* aos = (uint32_t*)st.aos.p + 5 * (size_t)first;  // the range being built
     HIP_TRY(hipEventRecord(st.ev0, s));
     if (n > 0) {
-        prep_kernel<<<blocks(n, kBlock), kBlock, 0, s>>>((const uint32_t*)st.aos.p, n, (float4*)st.geo[0].p,
+        prep_kernel<<<blocks(n, kBlock), kBlock, 0, s>>>(aos, n, (float4*)st.geo[0].p,
                                                         (uint32_t*)st.col[0].p, (int*)st.nof[0].p, ctl);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_ctl, ctl, kCtlWords * 4, hipMemcpyDeviceToHost, s));
@@ -801,8 +808,8 @@ int device_build(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int s
         off += cnt;
         cnt = 2 * inner;
     }
-    const size_t total = (size_t)off + (size_t)cnt;
-    rc = ensure(st.out, total * sizeof(mirt_node));
+    const size_t total_nodes = (size_t)off + (size_t)cnt;
+    rc = ensure(st.out, total_nodes * sizeof(mirt_node));
     if (rc) return rc;
     BNode* nodes = (BNode*)st.nodes.p;
     const int nl = (int)level_off.size();
@@ -813,9 +820,19 @@ int device_build(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int s
                                                                    (mirt_node*)st.out.p);
     if (n > 0)
         finish_kernel<<<blocks(n, kBlock), kBlock, 0, s>>>((const float4*)st.geo[cur].p, (const uint32_t*)st.col[cur].p,
-                                                          n, (uint32_t*)st.aos.p);
+                                                          n, aos);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev1, s));
+    *out_count = (int)total_nodes;
+    *levels_out = nl;
+    return MIRT_OK;
+}
+
+// the built tree and the n reordered spheres (the first n of st.aos) to the host
+int download(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int count, mirt_node** out_nodes)
+{
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    const size_t total = (size_t)count;
     mirt_node* out = (mirt_node*)std::malloc(total * sizeof(mirt_node));
     if (!out) {
         (void)hipStreamSynchronize(s);
@@ -833,12 +850,42 @@ int device_build(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int s
         return hip_fail(e, "mirt_bvh_build_flat_device");
     }
     *out_nodes = out;
-    *out_count = (int)total;
-    *levels_out = nl;
     return MIRT_OK;
 }
 
 }  // namespace
+
+namespace mirt {
+
+int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start, int end, int depth,
+                   ResidentTree* out, int* declined)
+{
+    BuildState* st = nullptr;
+    if (int rc = get_state(c, &st)) return rc;
+    int count = 0, levels = 0;
+    if (int rc = device_build(c, *st, spheres, total, start, end - start, start, depth, &count, declined, &levels)) {
+        (void)hipStreamSynchronize((hipStream_t)mirt_ctx_stream(c));
+        return rc;
+    }
+    out->aos = (const uint32_t*)st->aos.p;
+    out->nodes = (const mirt_node*)st->out.p;
+    out->num_nodes = count;
+    out->levels = levels;
+    return MIRT_OK;
+}
+
+int build_resident_ms(mirt_ctx* c, float* ms)
+{
+    BuildState* st = *ctx_build_state(c);
+    if (!st || !st->ev0 || !st->ev1) {
+        set_error("mirt device build: no build has run on this context");
+        return MIRT_E_INVALID;
+    }
+    HIP_TRY(hipEventElapsedTime(ms, st->ev0, st->ev1));
+    return MIRT_OK;
+}
+
+}  // namespace mirt
 
 extern "C" {
 
@@ -858,9 +905,15 @@ try {
     BuildState* st = nullptr;
     if (int rc = get_state(c, &st)) return rc;
     st->have_stats = false;
-    int declined = 0, levels = 0;
-    int rc = device_build(c, *st, spheres + start, end - start, start, depth, out_nodes, out_count, &declined, &levels);
-    if (rc) return rc;
+    int declined = 0, levels = 0, count = 0;
+    const int n = end - start;
+    int rc = device_build(c, *st, spheres + start, n, 0, n, start, depth, &count, &declined, &levels);
+    if (!rc && !declined) rc = download(c, *st, spheres + start, n, count, out_nodes);
+    if (rc) {
+        (void)hipStreamSynchronize((hipStream_t)mirt_ctx_stream(c));
+        return rc;
+    }
+    if (!declined) *out_count = count;
     mirt_build_stats bs{};
     if (declined) {
         rc = mirt_bvh_build_flat(spheres, start, end, depth, out_nodes, out_count);

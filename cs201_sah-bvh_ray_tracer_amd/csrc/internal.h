@@ -38,6 +38,38 @@ int ctx_device(const mirt_ctx* c);
 struct BuildState;
 BuildState** ctx_build_state(mirt_ctx* c);
 void build_state_free(BuildState* st);
+// The same build left on the device (mirt_scene_build_device): all `total`
+// spheres are copied to the build's scratch, the tree of [start, end) is built
+// there, and *out points at the reordered 20-byte spheres and the flat nodes
+// in that scratch -- valid until the ctx's next build. The kernels are
+// enqueued on the ctx's stream, not waited for. *declined = 1: the input is
+// one the kernels decline, nothing was built. build_resident_ms: the device
+// time of that build, once the stream has been synchronised.
+struct ResidentTree {
+    const uint32_t* aos;
+    const mirt_node* nodes;
+    int num_nodes;
+    int levels;
+};
+int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start, int end, int depth,
+                   ResidentTree* out, int* declined);
+int build_resident_ms(mirt_ctx* c, float* ms);
+// render.hip: the scene arrays of a ctx (csrc/layout.h has the element types),
+// all device allocations the ctx owns, and the scalars that go with them.
+struct DeviceScene {
+    void *dnodes = nullptr, *nodes32 = nullptr, *geo = nullptr, *color = nullptr, *pnodes = nullptr,
+         *hnodes = nullptr, *haux = nullptr, *leaves = nullptr, *ndepth = nullptr;
+    int num_nodes = 0, num_spheres = 0;
+    uint32_t num_pnodes = 0, num_hnodes = 0, num_leaves = 0, wide_root = 0;
+    size_t leaf_box_off = 0;
+    bool encloses = false, ordered = false, leaf_big = false;
+    float r_max = 0.0f, c_max = 0.0f, o_bound = 0.0f;
+};
+// Installs `sc` in the ctx, which owns the arrays from here on: waits for the
+// ctx's enqueued frames, frees the scene it held (num_spheres = -1 until the
+// new one is in place), then takes the pointers and scalars.
+int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc);
+void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st);
 // [p, p + bytes) is ONE page-locked host range (mirt_host_alloc /
 // mirt_host_register): copies into it are DMA, asynchronous to the host.
 bool host_page_locked(const void* p, size_t bytes);

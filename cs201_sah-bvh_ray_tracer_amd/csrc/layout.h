@@ -1,7 +1,8 @@
 // The device layouts of a scene and the host-side record that holds them
 // (scene_layout.cpp builds it, mirt_scene_upload_flat copies it to the device,
-// trace.h walks it). No HIP in here: a plain host compiler builds this header
-// and scene_layout.cpp for the CPU tests and the sanitizer driver.
+// trace.h walks it; scene_device.hip derives the same bytes by kernels). No
+// HIP in here: a plain host compiler builds this header and scene_layout.cpp
+// for the CPU tests and the sanitizer driver.
 #pragma once
 #include <cstddef>
 #include <cstdint>

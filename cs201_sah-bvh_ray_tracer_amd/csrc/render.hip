@@ -1419,6 +1419,7 @@ struct mirt_ctx {
     char* d_leaves = nullptr;   // leaf spheres (float4 each), then at leaf_box_off the leaf boxes (LeafBox each)
     size_t leaf_box_off = 0;
     uint32_t num_hnodes = 0;
+    uint32_t num_pnodes = 0, num_leaves = 0;  // read back by mirt_scene_resident_layout
     uint32_t wide_root = 0;     // HNode a four-wide walk starts at (DevScene::wide_root)
     uint8_t* d_ndepth = nullptr;  // depth of every flat node (BVH overlay colours)
     uint32_t* d_overlay = nullptr;  // BVH overlay: per-pixel last line in draw order
@@ -1444,6 +1445,8 @@ struct mirt_ctx {
     int num_cus = 0;
     int debug_stall_ms = 0;     // MIRT_OPT_DEBUG_STALL_MS: test hook, each frame starts behind a bounded wait
     mirt::BuildState* build = nullptr;  // mirt_bvh_build_flat_device's scratch (bvh_device.hip)
+    mirt_scene_build_stats scene_stats{};  // of the last mirt_scene_build_device
+    bool have_scene_stats = false;
 };
 
 namespace {
@@ -1966,6 +1969,8 @@ try {
     c->num_nodes = nn;
     c->num_spheres = ns;
     c->num_hnodes = (uint32_t)lay.hnodes.size();
+    c->num_pnodes = (uint32_t)lay.pnodes.size();
+    c->num_leaves = (uint32_t)nl;
     c->leaf_box_off = lay.leaf_box_off;
     c->leaf_big = lay.leaf_big;
     c->wide_root = lay.wide_root;
@@ -1978,6 +1983,62 @@ try {
 } catch (const std::bad_alloc&) {
     set_error("mirt_scene_upload_flat: out of host memory");
     return MIRT_E_NOMEM;
+}
+
+int64_t mirt_scene_resident_layout(mirt_ctx* c, int part, void* out, size_t cap, mirt_scene_layout_info* info)
+{
+    if (!c) {
+        set_error("mirt_scene_resident_layout: null context");
+        return MIRT_E_INVALID;
+    }
+    if (!ctx_ok(c, true, "mirt_scene_resident_layout")) return MIRT_E_NOSCENE;
+    const size_t nn = (size_t)c->num_nodes, ns1 = (size_t)c->num_spheres + 1, nl = c->num_leaves;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (part) {
+    case MIRT_LAYOUT_DNODES: src = c->d_nodes, bytes = sizeof(DNode) * nn; break;
+    case MIRT_LAYOUT_GEO: src = c->d_geo, bytes = sizeof(float4) * ns1; break;
+    case MIRT_LAYOUT_COLOR: src = c->d_color, bytes = sizeof(uint32_t) * ns1; break;
+    case MIRT_LAYOUT_PNODES: src = c->d_pnodes, bytes = sizeof(PNode) * c->num_pnodes; break;
+    case MIRT_LAYOUT_HNODES: src = c->d_hnodes, bytes = sizeof(HNode) * c->num_hnodes; break;
+    case MIRT_LAYOUT_HAUX: src = c->d_haux, bytes = sizeof(HAux) * c->num_hnodes; break;
+    case MIRT_LAYOUT_LEAF_GEO: src = c->d_leaves, bytes = sizeof(float4) * nl; break;
+    case MIRT_LAYOUT_LEAF_BOX: src = c->d_leaves + c->leaf_box_off, bytes = sizeof(LeafBox) * nl; break;
+    case MIRT_LAYOUT_NDEPTH: src = c->d_ndepth, bytes = std::max<size_t>(nn, 1); break;
+    default: set_error("mirt_scene_resident_layout: unknown part %d", part); return MIRT_E_INVALID;
+    }
+    if (info) {
+        info->encloses = c->prune_ok;
+        info->ordered = c->ordered_ok;
+        info->leaf_big = c->leaf_big;
+        info->r_max = c->r_max;
+        info->c_max = c->c_max;
+        info->o_bound = c->o_bound;
+        info->num_pnodes = c->num_pnodes;
+        info->num_hnodes = c->num_hnodes;
+        info->num_leaves = c->num_leaves;
+        info->wide_root = c->wide_root;
+        info->leaf_box_off = c->leaf_box_off;
+    }
+    if (out && cap >= bytes && bytes) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    }
+    return (int64_t)bytes;
+}
+
+int mirt_last_scene_build_stats(mirt_ctx* c, mirt_scene_build_stats* out)
+{
+    if (!c || !out) {
+        set_error("mirt_last_scene_build_stats: null context or output");
+        return MIRT_E_INVALID;
+    }
+    if (!c->have_scene_stats) {
+        set_error("mirt_last_scene_build_stats: no mirt_scene_build_device has finished on this context");
+        return MIRT_E_INVALID;
+    }
+    *out = c->scene_stats;
+    return MIRT_OK;
 }
 
 int mirt_scene_upload(mirt_ctx* c, const mirt_sphere* spheres, int ns, const mirt_bvh_node* root)
@@ -2110,6 +2171,46 @@ int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_d
 }
 int ctx_device(const mirt_ctx* c) { return c->device; }
 BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
+int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
+{
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    void** held[] = {(void**)&c->d_nodes, (void**)&c->d_nodes32, (void**)&c->d_geo, (void**)&c->d_color,
+                     (void**)&c->d_pnodes, (void**)&c->d_hnodes, (void**)&c->d_haux, (void**)&c->d_leaves,
+                     (void**)&c->d_ndepth};
+    for (void** p : held) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c->num_spheres = -1;
+    c->d_nodes = (DNode*)sc.dnodes;
+    c->d_nodes32 = (mirt_node*)sc.nodes32;
+    c->d_geo = (float4*)sc.geo;
+    c->d_color = (uint32_t*)sc.color;
+    c->d_pnodes = (PNode*)sc.pnodes;
+    c->d_hnodes = (HNode*)sc.hnodes;
+    c->d_haux = (HAux*)sc.haux;
+    c->d_leaves = (char*)sc.leaves;
+    c->d_ndepth = (uint8_t*)sc.ndepth;
+    c->num_nodes = sc.num_nodes;
+    c->num_hnodes = sc.num_hnodes;
+    c->num_pnodes = sc.num_pnodes;
+    c->num_leaves = sc.num_leaves;
+    c->leaf_box_off = sc.leaf_box_off;
+    c->leaf_big = sc.leaf_big;
+    c->wide_root = sc.wide_root;
+    c->ordered_ok = sc.ordered;
+    c->prune_ok = sc.encloses;
+    c->r_max = sc.r_max;
+    c->c_max = sc.c_max;
+    c->o_bound = sc.o_bound;
+    c->num_spheres = sc.num_spheres;
+    return MIRT_OK;
+}
+void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st)
+{
+    c->scene_stats = st;
+    c->have_scene_stats = true;
+}
 }  // namespace mirt
 
 extern "C" {

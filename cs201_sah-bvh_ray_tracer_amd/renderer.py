@@ -306,6 +306,62 @@ class Renderer:
         check(self.L.mirt_last_build_stats(self.h, C.byref(st)), "mirt_last_build_stats")
         return {k: getattr(st, k) for k, _ in abi.BuildStats._fields_}
 
+    def build_scene(self, spheres, start=0, end=None, depth=0):
+        """Spheres in, scene resident (mirt_scene_build_device): the tree of
+        spheres[start:end] is built and laid out on this context's device and
+        installed, as build_bvh + upload would leave it, without the tree
+        leaving the device. `spheres` is not written; returns the spheres as
+        reordered (what hit records index). last_scene_build_stats() says how
+        it went."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        end = len(spheres) if end is None else end
+        out = np.zeros(len(spheres), abi.SPHERE)
+        check(self.L.mirt_scene_build_device(self.h, ptr(spheres), len(spheres), start, end, depth, ptr(out)),
+              "mirt_scene_build_device")
+        self.num_spheres = len(spheres)
+        return out
+
+    def upload_device(self, spheres, bvh=None):
+        """upload() of a Bvh (or an abi.NODE array, or None) with the layouts
+        derived on the device (mirt_scene_upload_flat_device): only the raw
+        spheres and nodes cross the link."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        nodes = np.zeros(0, abi.NODE) if bvh is None else bvh.nodes if isinstance(bvh, Bvh) else bvh
+        nodes = np.ascontiguousarray(nodes, abi.NODE)
+        check(self.L.mirt_scene_upload_flat_device(self.h, ptr(spheres) if len(spheres) else None, len(spheres),
+                                                   ptr(nodes) if len(nodes) else None, len(nodes)),
+              "mirt_scene_upload_flat_device")
+        self.num_spheres = len(spheres)
+
+    def resident_layout(self):
+        """mirt_scene_resident_layout: the layouts of the scene this context
+        holds, read back from the device; (info, parts) shaped like
+        scene_layout()'s."""
+        raw = abi.SceneLayoutInfo()
+        size = {}
+        for part, (name, dtype) in enumerate(abi.LAYOUT_PARTS):
+            size[name] = check(self.L.mirt_scene_resident_layout(self.h, part, None, 0, C.byref(raw)),
+                               "mirt_scene_resident_layout")
+        parts = {}
+        for part, (name, dtype) in enumerate(abi.LAYOUT_PARTS):
+            if size[name] % dtype.itemsize:
+                raise MirtError(f"mirt_scene_resident_layout: part {name} is {size[name]} bytes")
+            out = np.zeros(size[name] // dtype.itemsize, dtype)
+            got = check(self.L.mirt_scene_resident_layout(self.h, part, ptr(out), out.nbytes, None),
+                        "mirt_scene_resident_layout")
+            if got != out.nbytes:
+                raise MirtError(f"mirt_scene_resident_layout: part {name} is {got} bytes, expected {out.nbytes}")
+            parts[name] = out
+        return {name: getattr(raw, name) for name, _ in raw._fields_}, parts
+
+    def last_scene_build_stats(self):
+        """mirt_scene_build_stats of the last build_scene on this context, as a
+        dict: on_device (0: input declined, host build and host upload ran),
+        levels, nodes, build_ms, layout_ms, total_ms."""
+        st = abi.SceneBuildStats()
+        check(self.L.mirt_last_scene_build_stats(self.h, C.byref(st)), "mirt_last_scene_build_stats")
+        return {k: getattr(st, k) for k, _ in abi.SceneBuildStats._fields_}
+
     # ---- frames
     def render_frame(self, cam, width, height, depth=5, use_bvh=True, seed=1, sample=0, accumulate=False,
                      frames=1, row_block=8, shard=0, num_shards=1, samples=1, jitter=False):

@@ -251,6 +251,43 @@ typedef struct mirt_build_stats {
 /* Of the ctx's last finished mirt_bvh_build_flat_device (MIRT_E_INVALID: none). */
 int mirt_last_build_stats(mirt_ctx *ctx, mirt_build_stats *out);
 
+/* ------------------------------ device: spheres in, scene resident (mirt 0.8) */
+
+/* Build and lay out a scene on the device of ctx in one call: the tree of
+   spheres[start, end) from `depth` is built by the kernels of
+   mirt_bvh_build_flat_device, the device layouts (csrc/layout.h) are derived
+   from it by kernels (csrc/scene_device.hip), byte for byte what
+   mirt_scene_upload_flat derives on the host, and the scene -- all num_spheres
+   spheres in reordered order, plus the sentinel -- is installed in the ctx. The
+   tree never leaves the device. Afterwards the ctx is as if
+   mirt_bvh_build_flat(copy, start, end, depth, ...) and
+   mirt_scene_upload_flat(ctx, copy, num_spheres, ...) had run. `spheres` is
+   not written; `reordered` (may be NULL) receives the num_spheres spheres as
+   reordered, which a caller needs to interpret mirt_hit.sphere. Frames already
+   enqueued on the ctx finish first. Inputs the device build declines (see
+   mirt_bvh_build_flat_device) take the host build and the host upload: the
+   result is the same (mirt_scene_build_stats.on_device = 0). Arguments are
+   checked as mirt_bvh_build_flat_device checks them, plus end <= num_spheres;
+   MIRT_E_INVALID comes before any HIP call. */
+int mirt_scene_build_device(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres, int start, int end,
+                            int depth, mirt_sphere *reordered);
+/* mirt_scene_upload_flat with the layouts derived on the device: same
+   contract, same host-side check of the tree, but only the raw spheres and
+   nodes cross the link (a tree from mirt_bvh_build_flat_cached, say). */
+int mirt_scene_upload_flat_device(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres,
+                                  const mirt_node *nodes, int num_nodes);
+
+typedef struct mirt_scene_build_stats {
+    int32_t on_device;   /* 1: built and laid out by the kernels; 0: input declined, host build + host upload */
+    int32_t levels;      /* tree levels the build processed (0 when on_device == 0) */
+    int32_t nodes;
+    float   build_ms;    /* HIP-event time of the build's kernels (0 when on_device == 0) */
+    float   layout_ms;   /* host clock over the layout kernels, their read-backs and allocations (0 likewise) */
+    float   total_ms;    /* call to return, host clock */
+} mirt_scene_build_stats;
+/* Of the ctx's last finished mirt_scene_build_device (MIRT_E_INVALID: none). */
+int mirt_last_scene_build_stats(mirt_ctx *ctx, mirt_scene_build_stats *out);
+
 /* ---------------------------------------------------------- rendering */
 
 /* Number of rows (and the row indices, if rows != NULL) a shard renders. */
@@ -401,6 +438,11 @@ enum { MIRT_LAYOUT_DNODES = 0, MIRT_LAYOUT_GEO = 1, MIRT_LAYOUT_COLOR = 2, MIRT_
        MIRT_LAYOUT_NDEPTH = 8 };
 int64_t mirt_scene_layout(const mirt_sphere *spheres, int num_spheres, const mirt_node *nodes, int num_nodes,
                           int part, void *out, size_t cap, mirt_scene_layout_info *info);
+/* The same parts and the same info read back from the ctx's resident scene,
+   whichever call installed it (waits for the ctx's stream): same part ids and
+   return convention. MIRT_E_NOSCENE without a scene, MIRT_E_INVALID for an
+   unknown part; a cap below the part's size writes nothing. */
+int64_t mirt_scene_resident_layout(mirt_ctx *ctx, int part, void *out, size_t cap, mirt_scene_layout_info *info);
 
 /* The camera ray of every pixel of the shard (ray.c:17-32 with the pixel
    mapping of main.c:356-365). */
