@@ -204,6 +204,9 @@ SIGNATURES = [
     ("mirt_any_hit_rays", I, [P, P, I, I, P]),
     ("mirt_sphere_pairs", I, [P, P, P, I, P]),
     ("mirt_aabb_pairs", I, [P, P, P, I, P]),
+    ("mirt_hemisphere_probe", I, [P, P, P, P, P, I, P, P]),
+    ("mirt_coop_geometry", I, [I, C.c_uint64, P, P, P, P]),
+    ("mirt_pixel_rows", I, [I, I, I, I, I, I, P, C.c_int64, P]),
     ("mirt_box_form_pairs", I, [P, P, P, P, I, I, P]),
     ("mirt_sphere_form_pairs", I, [P, P, P, P, I, I, P]),
     ("mirt_camera_rays", I, [P, P, P, P]),

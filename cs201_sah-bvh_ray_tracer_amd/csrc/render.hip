@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "coop.h"
 #include "internal.h"
 #include "shard.h"
 #include "trace.h"
@@ -42,6 +43,7 @@ struct FrameConst {
     int num_rows;      // rows of this launch: shard_rows x samples (frame j's rows follow frame j-1's)
     int shard_rows;    // rows of one frame of this shard
     int samples;       // frames in this launch (RNG samples sample .. sample + samples - 1)
+    RowMagic magic;    // width, shard_rows and row_block as multiply-high divisors (coop.h)
 };
 
 FrameConst make_frame_const(const mirt_camera* cam, const mirt_frame_desc* fd)
@@ -75,21 +77,20 @@ FrameConst make_frame_const(const mirt_camera* cam, const mirt_frame_desc* fd)
     f.samples = fd->samples > 1 ? fd->samples : 1;
     f.jitter = fd->jitter != 0;
     f.num_rows = f.shard_rows * f.samples;
+    f.magic = row_magic_make(f.width, f.shard_rows, f.row_block);
     return f;
 }
 
 // Image row of launch row r (compacted shard row r % shard_rows of frame r / shard_rows).
 __device__ __forceinline__ int shard_row_to_y(const FrameConst& f, int r)
 {
-    if (f.samples > 1) r %= f.shard_rows;
-    const int blk = r / f.row_block;
-    return shard_block(f.shard, blk, f.num_shards, f.lead_skip) * f.row_block + (r - blk * f.row_block);
+    return magic_row_to_y(f.magic, r, f.samples, f.shard_rows, f.row_block, f.shard, f.num_shards, f.lead_skip);
 }
 
 // RNG contract sample of launch row r (one sample per frame).
 __device__ __forceinline__ uint32_t row_sample(const FrameConst& f, int r)
 {
-    return f.samples > 1 ? f.sample + (uint32_t)(r / f.shard_rows) : f.sample;
+    return f.samples > 1 ? f.sample + magic_div((uint32_t)r, (uint32_t)f.shard_rows, f.magic.shard_rows) : f.sample;
 }
 
 // main.c:362-365 + ray.c:26-31 for pixel (x, y) of RNG sample `sample`.
@@ -579,7 +580,7 @@ inline size_t bounce_lds_bytes(int depth) { return sizeof(uint32_t) * 256 * (siz
 // shaded rather than held in two registers for the whole walk.
 __device__ __forceinline__ uint64_t chain_key(const FrameConst& f, uint32_t pixel)
 {
-    const int r = (int)(pixel / (uint32_t)f.width), x = (int)(pixel - (uint32_t)r * (uint32_t)f.width);
+    const int r = (int)magic_div(pixel, (uint32_t)f.width, f.magic.width), x = (int)(pixel - (uint32_t)r * (uint32_t)f.width);
     return pixel_key(f.seed, (uint32_t)(shard_row_to_y(f, r) * f.width + x), row_sample(f, r));
 }
 
@@ -792,28 +793,69 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
                 if (has && w.walking()) w.template step<FAST>(sc, sr, sp, pr, stk, best_t, best_s, cnt);
             }
         }
-        // shade every lane whose ray is done
-        if (has && !w.walking()) {
+        // shade every lane whose ray is done: shade_level in three steps, so
+        // that the wave samples the new directions together (hemisphere_wave;
+        // the lanes still walking only help). (a) per lane: the level's colour,
+        // and either the end of the chain (pixel folded and stored) or the hit
+        // point (into the ray's origin), the normal and the pixel's RNG key
+        //
+        // WALK 4 (batched leaf loads, trees past the L2) keeps the per-lane
+        // shade_level: it already spills at 96 VGPRs, and the wave form's
+        // temporaries put three more registers into scratch (44 -> 56 B) with
+        // reloads inside the walk.
+        bool go = false;  // this lane's chain goes on: it needs a direction
+        float nn[3] = {0.0f, 0.0f, 0.0f};
+        uint64_t key = 0;
+        if constexpr (WALK == 4) {
+            if (has && !w.walking()) {
+                go = shade_level(sc, f, ray, best_t, best_s, level, k, chain_key(f, pixel), cs, cstride, base0, pixel,
+                                 out, acc, true);
+                has = go;
+            }
+        } else if (has && !w.walking()) {
             if (DIAG) {
                 dg_walk_max = max(dg_walk_max, dg_steps);
                 dg_chain += dg_steps;
                 dg_steps = 0;
             }
-            if (shade_level(sc, f, ray, best_t, best_s, level, k, chain_key(f, pixel), cs, cstride, base0, pixel, out,
-                            acc, true)) {
-                sr = bounce_slab_ray(sc, ray);
-                sp = sph_ray(ray);
-                w.start(sc);
-                best_t = INFINITY;
-                best_s = -1;
-                pr = prune_off();
+            uint32_t tail = 255u << 24;  // depth exhausted: black (renderer.c:23-24)
+            int stored = level - 1;
+            if (best_s < 0) {
+                tail = sky_rgba(ray.dy);
             } else {
+                cs[(level - 1) * cstride] = sc.color[best_s];
+                stored = level;
+                if (level + 1 < f.depth) {  // trace_ray(bounce, depth - 1) still has depth
+                    float p[3];
+                    hit_point_normal(ray, best_t, sc.geo[best_s], p, nn);
+                    ray.ox = p[0];
+                    ray.oy = p[1];
+                    ray.oz = p[2];
+                    key = chain_key(f, pixel);
+                    level++;
+                    go = true;
+                }
+            }
+            if (!go) {
+                uint32_t c = tail;
+                for (int l = stored - 1; l >= 0; l--) c = blend_rgba(cs[l * cstride], c);
+                store_pixel(f, out, acc, pixel, blend_rgba(base0, c));
                 has = false;
                 if (DIAG) {
                     dg_chain_max = max(dg_chain_max, dg_chain);
                     dg_chain = 0;
                 }
             }
+        }
+        // (b) the wave-uniform sampling, (c) per lane: the walk of the next level
+        if (WALK != 4 && __ballot(go)) hemisphere_wave(key, k, nn, go, ray.dx, ray.dy, ray.dz);
+        if (go) {
+            sr = bounce_slab_ray(sc, ray);
+            sp = sph_ray(ray);
+            w.start(sc);
+            best_t = INFINITY;
+            best_s = -1;
+            pr = prune_off();
         }
     }
     if constexpr (LANE4) {
@@ -1143,6 +1185,23 @@ __global__ void aabb_pairs_kernel(const mirt_ray* __restrict__ rays, const mirt_
     const Ray ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
     const mirt_aabb b = boxes[i];
     out[i] = slab_test(slab_ray(ray), b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z) ? 1 : 0;
+}
+
+// hemisphere_wave on caller-given lanes (mirt_hemisphere_probe): the grid
+// covers the lanes exactly, so every wave is whole and calls it uniformly.
+__global__ void hemisphere_probe_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ k0,
+                                        const float* __restrict__ normals, const int32_t* __restrict__ need,
+                                        float* __restrict__ dir, uint32_t* __restrict__ kout)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float n[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    float x = dir[3 * i], y = dir[3 * i + 1], z = dir[3 * i + 2];
+    uint32_t k = k0[i];
+    hemisphere_wave(keys[i], k, n, need[i] != 0, x, y, z);
+    dir[3 * i] = x;
+    dir[3 * i + 1] = y;
+    dir[3 * i + 2] = z;
+    kout[i] = k;
 }
 
 // The walks' filtered box tests on pairs (mirt_box_form_pairs): the Prune
@@ -2757,6 +2816,36 @@ int mirt_aabb_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_aabb* boxes, i
                                                              (int32_t*)c->d_res);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_hemisphere_probe(mirt_ctx* c, const uint64_t* keys, const uint32_t* k0, const float* normals,
+                          const int32_t* need, int n, float* out_dir, uint32_t* out_k)
+{
+    if (!ctx_ok(c, false, "mirt_hemisphere_probe")) return MIRT_E_INVALID;
+    if (!keys || !k0 || !normals || !need || !out_dir || !out_k || (n != 64 && (n <= 0 || n % 256 != 0))) {
+        set_error("mirt_hemisphere_probe: invalid arguments (n is 64 or a multiple of 256)");
+        return MIRT_E_INVALID;
+    }
+    const size_t sn = (size_t)n, kb = 8 * sn, wb = 4 * sn, vb = 12 * sn;
+    int rc = ensure(&c->d_in, &c->in_cap, kb + wb + vb + wb);
+    if (!rc) rc = ensure(&c->d_res, &c->res_cap, vb + wb);
+    if (rc) return rc;
+    char* din = (char*)c->d_in;
+    char* dres = (char*)c->d_res;
+    HIP_TRY(hipMemcpyAsync(din, keys, kb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + kb, k0, wb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + kb + wb, normals, vb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din + kb + wb + vb, need, wb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dres, out_dir, vb, hipMemcpyHostToDevice, c->stream));
+    const int threads = n == 64 ? 64 : 256;
+    hemisphere_probe_kernel<<<n / threads, threads, 0, c->stream>>>(
+        (const uint64_t*)din, (const uint32_t*)(din + kb), (const float*)(din + kb + wb),
+        (const int32_t*)(din + kb + wb + vb), (float*)dres, (uint32_t*)(dres + vb));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_dir, dres, vb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_k, dres + vb, wb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MIRT_OK;
 }

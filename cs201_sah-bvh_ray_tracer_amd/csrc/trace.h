@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "../../include/mirt.h"
+#include "coop.h"
 #include "layout.h"
 #include "rng.h"
 
@@ -1530,6 +1531,99 @@ __device__ __forceinline__ void hemisphere(uint64_t key, uint32_t& k, const floa
         x = x * -1.0f;
         y = y * -1.0f;
         z = z * -1.0f;
+    }
+}
+
+// One try of hemisphere()'s loop: the draws k, k + 1, k + 2 of the stream, by
+// the same expressions; true if the point is accepted.
+__device__ __forceinline__ bool hemisphere_try(uint64_t key, uint32_t k, float& x, float& y, float& z)
+{
+    x = -1.0f + ((float)draw(key, k) / 2147483648.0f) * 2.0f;
+    y = -1.0f + ((float)draw(key, k + 1u) / 2147483648.0f) * 2.0f;
+    z = -1.0f + ((float)draw(key, k + 2u) / 2147483648.0f) * 2.0f;
+    const float l2 = dot3(x, y, z, x, y, z);
+    return l2 < 1.0f && l2 != 0.0f;
+}
+
+// hemisphere() for a whole wave. Called by all 64 lanes in wave-uniform
+// control flow; a lane with `need` gets, bit for bit, what hemisphere(key, k,
+// n, x, y, z) gives it (the first accepted try in index order, k advanced
+// past it), the others keep their k, x, y, z and only help.
+//
+// hemisphere()'s loop runs until the wave's unluckiest lane accepts (a try is
+// accepted with probability pi / 6: 1.9 tries per lane, 6-7 for the slowest
+// of 64). The stream is random-access (rng.h), so any lane can compute any
+// try of any other: after every sampling lane's own first try, the lanes that
+// are still pending ("owners") share out the wave -- coop.h: owner of rank r
+// gets the aligned group of g lanes r g .. r g + g - 1, lane i of it computes
+// the owner's next try number i % g from the owner's key and k (over the lane
+// crossbar: no LDS), and the owner takes the lowest accepted try of its
+// group from the ballot or moves on by g tries. Above 32 owners g is 1 and
+// each owner simply tries again itself. A full wave takes about three rounds
+// (64 -> ~30 pending -> g = 2 -> ~7 -> g = 8 -> done).
+//
+// The loop ends after kHemisphereRounds rounds whatever the draws: every
+// lane then had at least that many tries (hemisphere()'s own cap, never
+// reached: 0.476^4096), and a lane still pending keeps its latest own try.
+constexpr int kHemisphereRounds = 4096;
+__device__ __forceinline__ void hemisphere_wave(uint64_t key, uint32_t& k, const float* n, bool need, float& x,
+                                                float& y, float& z)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    bool open = false;  // samples, and no try accepted yet
+    if (need) {
+        open = !hemisphere_try(key, k, x, y, z);
+        k += 3u;
+    }
+    uint64_t pending = __ballot(open);
+    for (int round = 1; pending && round < kHemisphereRounds; round++) {
+        const uint32_t np = (uint32_t)__popcll(pending);
+        if (np > 32u) {  // g = 1: every owner is its own group
+            if (open) {
+                open = !hemisphere_try(key, k, x, y, z);
+                k += 3u;
+            }
+        } else {
+            const uint32_t shift = coop_group_shift(np);  // wave-uniform, >= 1
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pending >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)pending, 0u));
+            // every owner sends its lane number to the first lane of its
+            // group; the other lanes send to lane 1, which heads no group
+            // (g >= 2) and whose received word nobody reads
+            const int head = __builtin_amdgcn_ds_permute((int)((open ? rank << shift : 1u) << 2), (int)lane);
+            const int from = __builtin_amdgcn_ds_bpermute((int)((lane >> shift << shift) << 2), head) << 2;
+            const bool serves = coop_lane_rank(lane, shift) < np;  // else `from` is lane 0: in bounds, unused
+            const uint32_t klo = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)key);
+            const uint32_t khi = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)(key >> 32));
+            const uint32_t k0 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)k);
+            float tx, ty, tz;
+            const bool ok = hemisphere_try(((uint64_t)khi << 32) | klo, k0 + 3u * coop_lane_try(lane, shift), tx, ty, tz);
+            const uint64_t accepted = __ballot(ok && serves);
+            const int first = coop_first_accept(accepted, rank, shift);
+            const bool won = open && first >= 0;
+            const int win = (int)(won ? (rank << shift) + (uint32_t)first : lane) << 2;
+            tx = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute(win, (int)__float_as_uint(tx)));
+            ty = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute(win, (int)__float_as_uint(ty)));
+            tz = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute(win, (int)__float_as_uint(tz)));
+            if (won) {
+                x = tx;
+                y = ty;
+                z = tz;
+                k += 3u * (uint32_t)(first + 1);
+                open = false;
+            } else if (open) {
+                k += 3u << shift;
+            }
+        }
+        pending = __ballot(open);
+    }
+    if (need) {
+        normalize3(x, y, z);
+        if (!(dot3(x, y, z, n[0], n[1], n[2]) > 0.0f)) {
+            x = x * -1.0f;
+            y = y * -1.0f;
+            z = z * -1.0f;
+        }
     }
 }
 

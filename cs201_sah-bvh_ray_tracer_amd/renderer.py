@@ -560,6 +560,23 @@ class Renderer:
                                             ptr(out)), "mirt_sphere_form_pairs")
         return out.view(np.float32)
 
+    def hemisphere_probe(self, keys, k0, normals, need, out_dir):
+        """mirt_hemisphere_probe: the kernels' wave-cooperative bounce sampling
+        on len(keys) lanes (64, or a multiple of 256). Returns (dir, k):
+        float32 (n, 3) directions, starting from `out_dir` (lanes with need ==
+        0 keep theirs), and uint32 draws consumed."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        k0 = np.ascontiguousarray(k0, np.uint32)
+        normals = np.ascontiguousarray(normals, np.float32)
+        need = np.ascontiguousarray(need, np.int32)
+        d = np.array(out_dir, np.float32, order="C")
+        n = len(keys)
+        assert k0.shape == (n,) and need.shape == (n,) and normals.shape == (n, 3) and d.shape == (n, 3)
+        k = np.zeros(n, np.uint32)
+        check(self.L.mirt_hemisphere_probe(self.h, ptr(keys), ptr(k0), ptr(normals), ptr(need), n, ptr(d), ptr(k)),
+              "mirt_hemisphere_probe")
+        return d, k
+
     def partition_probe(self, centre, seg, split):
         """The device build's partition on caller-given keys: segments
         [seg[k], seg[k+1]) of `centre`, each partitioned by centre < split[k];

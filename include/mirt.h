@@ -389,6 +389,34 @@ int mirt_any_hit_rays(mirt_ctx *ctx, const mirt_ray *rays, int n, int use_bvh, i
 int mirt_sphere_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_sphere *spheres, int n, mirt_hit *out);
 int mirt_aabb_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_aabb *boxes, int n, int32_t *out);
 
+/* The kernels' wave-cooperative bounce sampling on caller-given lanes (test
+   probe; needs no scene). Lane i has RNG key keys[i], has consumed k0[i] draws
+   and, where need[i] != 0, samples a direction in the hemisphere of
+   normals[3i..]: out_dir[3i..] becomes that direction and out_k[i] the draws
+   consumed after it. A lane with need[i] == 0 only helps: its out_dir keeps
+   what the caller put there and its out_k is k0[i]. n lanes are launched as
+   one workgroup of 64 threads (n == 64) or n / 256 workgroups of 256 threads
+   (n a multiple of 256); any other n is MIRT_E_INVALID. */
+int mirt_hemisphere_probe(mirt_ctx *ctx, const uint64_t *keys, const uint32_t *k0, const float *normals,
+                          const int32_t *need, int n, float *out_dir, uint32_t *out_k);
+
+/* Host only, no ctx: the index math the kernels share with the host.
+   mirt_coop_geometry: the sampling groups of a wave with num_pending pending
+   lanes (1..64) -- *group = the group size g, lane_rank[i] / lane_try[i]
+   (64 each) = the rank of the owner lane i serves (>= num_pending: none) and
+   the try offset it computes, first_accept[r] (num_pending entries) = the
+   lowest try offset owner r's group accepted according to the ballot
+   `accepted` (bit i: lane i accepted), -1 if none.
+   mirt_pixel_rows: for each shard pixel index p = r * width + x of a launch
+   of `samples` frames of shard_rows rows each (row blocks of row_block rows,
+   shard `shard` of num_shards, lead_skip 0): out[4i..] = {r, x, the image row
+   y of launch row r, r / shard_rows}, by the multiply-high divisions of the
+   kernels. */
+int mirt_coop_geometry(int num_pending, uint64_t accepted, int32_t *group, int32_t *lane_rank, int32_t *lane_try,
+                       int32_t *first_accept);
+int mirt_pixel_rows(int width, int shard_rows, int samples, int row_block, int shard, int num_shards,
+                    const uint32_t *pixels, int64_t n, int32_t *out);
+
 /* Diagnostic surface (tests; not part of the stable ABI): the walks' FILTERED
    forms of the two tests above on pairs -- the same device functions the
    kernels call, so their error bounds can be checked pair by pair against
