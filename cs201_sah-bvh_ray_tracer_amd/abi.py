@@ -256,6 +256,8 @@ OPT_TRAVERSAL, OPT_FAST_SLAB, OPT_BLOCK_WAVES, OPT_DEFER, OPT_BOUNCE_THRESHOLD, 
     1, 2, 3, 4, 5, 6, 7)
 OPT_BOUNCE_BLOCKS, OPT_QUAD_DRAIN, OPT_LEAF_BATCH, OPT_QUAD_BATCH, OPT_ZERO_COPY = 9, 11, 14, 15, 17
 OPT_QUEUE_ORDER, OPT_DEBUG_STALL_MS = 18, 19
+OPT_CONFIRM_ONCE, OPT_DEBUG_FAIL_CONFIRM = 21, 22
+BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4
 MULTI_COPY, MULTI_HOST_DIRECT, MULTI_QUEUE_AHEAD = 1, 2, 4

@@ -316,7 +316,7 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t mask)
 #define MIRT_HCACHE 16
 #endif
 constexpr uint32_t kHCache = MIRT_HCACHE;
-constexpr int kBounceDiag = 12;  // mirt_bounce_stats words per wave  // HNodes staged in LDS per bounce workgroup (64 B each)
+constexpr int kBounceDiag = MIRT_BOUNCE_STATS_WORDS;  // mirt_bounce_stats words per wave  // HNodes staged in LDS per bounce workgroup (64 B each)
 
 // The bounce queue's control words: {records written} in the first 128-B
 // line, then one read head per queue SEGMENT, each in its own line. The
@@ -551,15 +551,15 @@ struct WideBounceWalk {  // WALK 2: four-wide; 4: four-wide, a step's leaf spher
     __device__ void start(const DevScene& sc) { w = wide_walk_start(sc, true); }
     __device__ void stop() { w = WideWalk{kPNone, 0u, 0u}; }
     __device__ bool walking() const { return wide_walking(w); }
-    template <bool FAST>
+    template <bool FAST, bool GD = false, bool DEFER = false>
     __device__ void step(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr, uint32_t* stk,
-                         float& bt, int& bs, Counters& cnt)
+                         float& bt, int& bs, Counters& cnt, GateDiag* gd = nullptr, int* lvl = nullptr)
     {
         // the bounded test in WALK 2; WALK 4 (trees past the L2) keeps the
         // margins: with its batched leaf loads the bounded form spills more
         // (4K/1M: -8%, MEASUREMENTS.md §D)
-        wide_lane_step<FAST, false, WALK == 4, kBoundedSlab && WALK != 4>(sc, sr, sp, pr, w, stk, bt, bs, cnt, hc,
-                                                                          hc_n);
+        wide_lane_step<FAST, false, WALK == 4, kBoundedSlab && WALK != 4, GD, DEFER>(sc, sr, sp, pr, w, stk, bt, bs,
+                                                                                     cnt, hc, hc_n, gd, lvl);
     }
 };
 template <>
@@ -569,7 +569,12 @@ struct BounceWalk<4> : WideBounceWalk<4> {};
 
 // DIAG (mirt_bounce_stats): per wave {loop iterations, walking lanes summed
 // over them, the same two after the queue ran dry, start / queue-dry / end
-// time (100 MHz clock), longest chain << 32 | longest walk (in steps)}.
+// time (100 MHz clock), longest chain << 32 | longest walk (in steps)}, and
+// of the lane loop's leaf gates (trace.h GateDiag; WALK 2, the lane loop
+// only): gate executions, those in which any lane ran the f64 t / loaded the
+// LeafBox, the lanes that did, and the loop iterations that held a gate / an
+// f64 t / a LeafBox load; then the closest hits confirmed, the confirmations
+// that failed, and the walks restarted in exact mode for a DFS segment.
 
 // Dynamic LDS of a bounce launch: the colour stack's rows for a frame of
 // `depth` levels (bounce levels 1 .. depth - 1 store a colour each).
@@ -627,9 +632,8 @@ __device__ __forceinline__ void solo_chain(const DevScene& sc, const FrameConst&
                                         int best_s, Prune pr, QuadWalk qw, int level, uint32_t k, uint32_t pixel,
                                         uint32_t base0, uint32_t src, uint32_t* wst, uint32_t* wcs,
                                         uint32_t* __restrict__ out, float* __restrict__ acc, lds_uint4* hc,
-                                        uint32_t hc_n)
+                                        uint32_t hc_n, uint32_t lane = threadIdx.x & 63)
 {
-    const uint32_t lane = threadIdx.x & 63;
     auto bu = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l0); };
     auto bf = [&](float v) { return __uint_as_float(bu(__float_as_uint(v))); };
     ray = Ray{bf(ray.ox), bf(ray.oy), bf(ray.oz), bf(ray.dx), bf(ray.dy), bf(ray.dz)};
@@ -652,7 +656,7 @@ __device__ __forceinline__ void solo_chain(const DevScene& sc, const FrameConst&
     SphRay sp = sph_ray(ray);
     SoloWalk w{lane < 4 ? cur : kPNone, lane < 4 ? end : 0u, top};
     for (;;) {
-        while (solo_step<FAST, kWideStack * 64, BND>(sc, sr, sp, pr, w, wst, best_t, best_s, hc, hc_n)) {
+        while (solo_step<FAST, kWideStack * 64, BND>(sc, sr, sp, pr, w, wst, best_t, best_s, hc, hc_n, lane)) {
         }
         if (!shade_level(sc, f, ray, best_t, best_s, level, k, chain_key(f, pixel), cs, kWideStride, base0, pixel, out,
                          acc, lane == 0))
@@ -682,13 +686,21 @@ template <bool FAST, int WALK, bool DIAG = false>
 __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene sc, FrameConst f, uint32_t* __restrict__ out,
                                                      float* __restrict__ acc, const BounceRec* __restrict__ queue,
                                                      uint32_t* __restrict__ qctl, int threshold, int quad_drain,
+                                                     int lvl_mode, int fail_n,
                                                      uint64_t* __restrict__ diag = nullptr)
 {
     uint64_t dg_it = 0, dg_lanes = 0, dg_it_x = 0, dg_lanes_x = 0, dg_tx = 0, dg_qit = 0, dg_tq = 0;
     const uint64_t dg_t0 = DIAG ? __builtin_amdgcn_s_memrealtime() : 0;
     uint32_t dg_steps = 0, dg_chain = 0, dg_walk_max = 0, dg_chain_max = 0;
-    uint64_t dg_seg = 0, dg_fb = 0;
+    uint64_t dg_seg = 0, dg_fb = 0, dg_it_gate = 0, dg_it_t = 0, dg_it_box = 0;
+    uint32_t dg_conf = 0, dg_conf_fail = 0, dg_fb_exact = 0;
+    GateDiag gd{0, 0, 0, 0, 0, false, false, false};
     constexpr bool LANE4 = WALK == 2 || WALK == 4;  // four-wide, one ray per lane
+    // the lane loop's walks confirm their closest hit once, when the level is
+    // shaded (trace.h wide_leaf_once); a lane whose `level` holds kExactWalk
+    // confirms every candidate at once -- every lane when lvl_mode is
+    // kExactWalk (MIRT_OPT_CONFIRM_ONCE 0) instead of 0
+    constexpr bool DEFER = FAST && WALK == 2;
     constexpr int cstride = 256;
     // the colour stack: one row per bounce level that can store a colour
     // (levels 1 .. depth - 1), sized at launch (bounce_lds_bytes): a depth-5
@@ -708,8 +720,15 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
         for (uint32_t i = threadIdx.x; i < 4 * hc_n; i += blockDim.x) hcache[i] = src[i];
         __syncthreads();
     }
-    uint32_t* cs = cstack + threadIdx.x;
-    uint32_t* stk = wstack + (LANE4 ? threadIdx.x : 0);
+    // DEFER: the thread's index is held once, as the byte offset of its LDS
+    // columns, and every later use derives from that (the compiler otherwise
+    // keeps the index, its offset and its lane in a register each, and the
+    // deferred kernel has exactly none to spare: 96 VGPRs, no scratch)
+    uint32_t tid4 = threadIdx.x << 2;
+    if (DEFER) asm volatile("" : "+v"(tid4));
+    const uint32_t tid = DEFER ? tid4 >> 2 : threadIdx.x;
+    uint32_t* cs = DEFER ? (uint32_t*)((char*)cstack + tid4) : cstack + threadIdx.x;
+    uint32_t* stk = DEFER ? (uint32_t*)((char*)wstack + tid4) : wstack + (LANE4 ? threadIdx.x : 0);
     Counters cnt{0, 0, 0, 0, 0};
     const uint32_t n = __builtin_amdgcn_readfirstlane(qctl[0]);
     uint32_t seg = blockIdx.x % kQSeg, segs_left = kQSeg;  // wave-uniform
@@ -736,14 +755,14 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
             const uint32_t lo = (uint32_t)((uint64_t)n * seg / kQSeg);
             const uint32_t sz = (uint32_t)((uint64_t)n * (seg + 1) / kQSeg) - lo;
             uint32_t b = 0;
-            if ((threadIdx.x & 63) == leader) b = atomicAdd(&qctl[kQLine * (1 + seg)], (uint32_t)__popcll(need));
+            if ((tid & 63) == leader) b = atomicAdd(&qctl[kQLine * (1 + seg)], (uint32_t)__popcll(need));
             b = __builtin_amdgcn_readlane(b, leader);
             if (b + (uint32_t)__popcll(need) >= sz) {  // this segment is dry: the next one
                 seg = seg + 1 == kQSeg ? 0 : seg + 1;
                 if (--segs_left == 0) exhausted = true;
             }
             if (!has) {
-                const uint32_t lane0 = threadIdx.x & 63;
+                const uint32_t lane0 = tid & 63;
                 const uint32_t idx = b + (uint32_t)__popcll(need & ((1ull << lane0) - 1));
                 if (idx < sz) {
                     const BounceRec rec = queue[lo + idx];
@@ -753,7 +772,7 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
                     pixel = rec.pixel;
                     k = rec.k;
                     base0 = rec.base0;
-                    level = 1;
+                    level = DEFER ? 1 | lvl_mode : 1;
                     w.start(sc);
                     best_t = INFINITY;
                     best_s = -1;
@@ -765,9 +784,22 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
         }
         if (!__ballot(has)) break;
         if (DIAG && exhausted && !dg_tx) dg_tx = __builtin_amdgcn_s_memrealtime();
-        if (LANE4 && quad_drain && exhausted && __popcll(__ballot(has)) <= 16) break;  // -> quad drain
+        // -> quad drain (wave-uniform; DEFER: after the confirmations below,
+        // where the test is made again rather than held in scalar registers
+        // across the walk loop, which has none to spare)
+        auto to_drain = [&]() {
+            uint32_t busy = (uint32_t)__popcll(__ballot(has));
+            asm volatile("" : "+s"(busy));
+            return quad_drain && exhausted && busy <= 16;
+        };
+        bool skip_walk = false;
+        if constexpr (DEFER) {
+            skip_walk = to_drain();
+        } else {
+            if (LANE4 && quad_drain && exhausted && __popcll(__ballot(has)) <= 16) break;
+        }
         // walk until few lanes are still walking and the others can make progress
-        for (;;) {
+        if (!skip_walk) for (;;) {
             const uint64_t walking = __ballot(has && w.walking());
             if (!walking) break;
             if (__popcll(walking) < threshold &&
@@ -786,9 +818,19 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
                 // lane-steps spent in a DFS-segment fallback (the lane stack
                 // would have overflowed), and the fallbacks entered
                 const bool seg0 = has && w.walking() && w.w.end != 0;
-                if (has && w.walking()) w.template step<FAST>(sc, sr, sp, pr, stk, best_t, best_s, cnt);
+                gd.st_gate = gd.st_t = gd.st_box = false;
+                const int lvl0 = level;
+                if (has && w.walking())
+                    w.template step<FAST, true, DEFER>(sc, sr, sp, pr, stk, best_t, best_s, cnt, &gd, &level);
+                dg_fb_exact += (level != lvl0) ? 1u : 0u;
                 dg_seg += seg0 ? 1u : 0u;
                 dg_fb += (!seg0 && has && w.w.end != 0) ? 1u : 0u;
+                dg_it_gate += __ballot(gd.st_gate) ? 1u : 0u;
+                dg_it_t += __ballot(gd.st_t) ? 1u : 0u;
+                dg_it_box += __ballot(gd.st_box) ? 1u : 0u;
+            } else if constexpr (DEFER) {
+                if (has && w.walking())
+                    w.template step<FAST, false, true>(sc, sr, sp, pr, stk, best_t, best_s, cnt, nullptr, &level);
             } else {
                 if (has && w.walking()) w.template step<FAST>(sc, sr, sp, pr, stk, best_t, best_s, cnt);
             }
@@ -803,6 +845,37 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
         // shade_level: it already spills at 96 VGPRs, and the wave form's
         // temporaries put three more registers into scratch (44 -> 56 B) with
         // reloads inside the walk.
+        //
+        // First the winner of a deferred walk against its exact box (trace.h
+        // wide_leaf_once): a failure walks the level again in exact mode
+        // instead of shading it. At the hand-over to the quad drain, whose
+        // gates confirm every candidate at once and hold sphere indices, a
+        // lane still walking confirms its tentative best here as well (what
+        // it shut out loses to it) and, should that fail, walks the level
+        // again from the root in the drain.
+        if constexpr (DEFER) {
+            const bool handover = to_drain();
+            if (has && (handover || !w.walking()) && !(level & kExactWalk) && best_s >= 0) {
+                best_s = confirm_leaf(sc, sr, best_s);
+                // MIRT_OPT_DEBUG_FAIL_CONFIRM: a failure reported whatever the box says
+                if (fail_n) {
+                    uint32_t fn = (uint32_t)fail_n;
+                    asm volatile("" : "+s"(fn));  // the division stays here: no reciprocal held across the walks
+                    if (pixel % fn == 0) best_s = -1;
+                }
+                if (DIAG) {
+                    dg_conf++;
+                    dg_conf_fail += best_s < 0 ? 1u : 0u;
+                }
+                if (best_s < 0) {
+                    level |= kExactWalk;
+                    w.start(sc);
+                    best_t = INFINITY;
+                    pr = prune_off();
+                }
+            }
+            if (handover) break;
+        }
         bool go = false;  // this lane's chain goes on: it needs a direction
         float nn[3] = {0.0f, 0.0f, 0.0f};
         uint64_t key = 0;
@@ -813,6 +886,7 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
                 has = go;
             }
         } else if (has && !w.walking()) {
+            if (DEFER) level &= ~kExactWalk;  // this level's walk is over
             if (DIAG) {
                 dg_walk_max = max(dg_walk_max, dg_steps);
                 dg_chain += dg_steps;
@@ -848,7 +922,7 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
             }
         }
         // (b) the wave-uniform sampling, (c) per lane: the walk of the next level
-        if (WALK != 4 && __ballot(go)) hemisphere_wave(key, k, nn, go, ray.dx, ray.dy, ray.dz);
+        if (WALK != 4 && __ballot(go)) hemisphere_wave(key, k, nn, go, ray.dx, ray.dy, ray.dz, tid & 63);
         if (go) {
             sr = bounce_slab_ray(sc, ray);
             sp = sph_ray(ray);
@@ -856,13 +930,15 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
             best_t = INFINITY;
             best_s = -1;
             pr = prune_off();
+            if (DEFER) level |= lvl_mode;
         }
     }
+    if constexpr (DEFER) level &= ~kExactWalk;  // the drain's walks are all exact
     if constexpr (LANE4) {
         // quad drain (uniform control flow here: every lane is active)
         const uint64_t busy = __ballot(has);
         if (busy) {
-            const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+            const uint32_t lane = tid & 63, wv = tid >> 6;
             if (has) qsrc[wv * 16 + lanes_below(busy)] = lane;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -887,8 +963,8 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
             sr = bounce_slab_ray(sc, ray);
             sp = sph_ray(ray);
             // the ray's LDS stacks stay in its source lane's columns
-            uint32_t* qstk = wstack + (threadIdx.x & ~63u) + src;
-            uint32_t* qcs = cstack + (threadIdx.x & ~63u) + src;
+            uint32_t* qstk = wstack + (tid & ~63u) + src;
+            uint32_t* qcs = cstack + (tid & ~63u) + src;
             if (DIAG) dg_tq = __builtin_amdgcn_s_memrealtime();
             while (__ballot(has)) {
                 if (DIAG) dg_qit++;
@@ -898,15 +974,15 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
                     if (__popcll(rays) == 1) {
                         solo_chain<FAST, kBoundedSlab && WALK != 4>(sc, f, __builtin_ctzll(rays), ray, best_t, best_s, pr,
                                                                     qw, level, k, pixel,
-                                         base0, src, wstack + (threadIdx.x & ~63u), cstack + (threadIdx.x & ~63u),
-                                         out, acc, (lds_uint4*)hcache, hc_n);
+                                         base0, src, wstack + (tid & ~63u), cstack + (tid & ~63u),
+                                         out, acc, (lds_uint4*)hcache, hc_n, lane);
                         break;
                     }
                 }
                 if (has && qw.cur != kPNone)
                     quad_step<FAST, kWideStride, kWideStack, kBoundedSlab && WALK != 4>(sc, sr, sp, pr, qw, qstk, best_t,
                                                                                         best_s,
-                                                             (lds_uint4*)hcache, hc_n);
+                                                             (lds_uint4*)hcache, hc_n, lane);
                 if (has && qw.cur == kPNone) {
                     if (shade_level(sc, f, ray, best_t, best_s, level, k, chain_key(f, pixel), qcs, kWideStride, base0, pixel, out,
                                     acc, (lane & 3) == 0)) {
@@ -928,8 +1004,8 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
             dg_walk_max = max(dg_walk_max, (uint32_t)__shfl_xor((int)dg_walk_max, o));
             dg_chain_max = max(dg_chain_max, (uint32_t)__shfl_xor((int)dg_chain_max, o));
         }
-        if ((threadIdx.x & 63) == 0) {
-            uint64_t* d = diag + kBounceDiag * (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+        if ((tid & 63) == 0) {
+            uint64_t* d = diag + kBounceDiag * (blockIdx.x * (blockDim.x >> 6) + (tid >> 6));
             d[0] = dg_it;
             d[1] = dg_lanes;
             d[2] = dg_it_x;
@@ -945,11 +1021,30 @@ __global__ __launch_bounds__(256) MIRT_BOUNCE_ATTR void bounce_kernel(DevScene s
         for (int o = 32; o; o >>= 1) {
             dg_seg += (uint64_t)__shfl_xor((long long)dg_seg, o);
             dg_fb += (uint64_t)__shfl_xor((long long)dg_fb, o);
+            gd.gates += (uint32_t)__shfl_xor((int)gd.gates, o);
+            gd.gates_t += (uint32_t)__shfl_xor((int)gd.gates_t, o);
+            gd.gates_box += (uint32_t)__shfl_xor((int)gd.gates_box, o);
+            gd.lanes_t += (uint32_t)__shfl_xor((int)gd.lanes_t, o);
+            gd.lanes_box += (uint32_t)__shfl_xor((int)gd.lanes_box, o);
+            dg_conf += (uint32_t)__shfl_xor((int)dg_conf, o);
+            dg_conf_fail += (uint32_t)__shfl_xor((int)dg_conf_fail, o);
+            dg_fb_exact += (uint32_t)__shfl_xor((int)dg_fb_exact, o);
         }
-        if ((threadIdx.x & 63) == 0) {
-            uint64_t* d = diag + kBounceDiag * (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+        if ((tid & 63) == 0) {
+            uint64_t* d = diag + kBounceDiag * (blockIdx.x * (blockDim.x >> 6) + (tid >> 6));
             d[10] = dg_seg;
             d[11] = dg_fb;
+            d[12] = gd.gates;
+            d[13] = gd.gates_t;
+            d[14] = gd.lanes_t;
+            d[15] = gd.gates_box;
+            d[16] = gd.lanes_box;
+            d[17] = dg_it_gate;
+            d[18] = dg_it_t;
+            d[19] = dg_it_box;
+            d[20] = dg_conf;
+            d[21] = dg_conf_fail;
+            d[22] = dg_fb_exact;
         }
     }
 }
@@ -1503,6 +1598,8 @@ struct mirt_ctx {
     size_t keys_cap = 0;
     int num_cus = 0;
     int debug_stall_ms = 0;     // MIRT_OPT_DEBUG_STALL_MS: test hook, each frame starts behind a bounded wait
+    int confirm_once = 2;       // MIRT_OPT_CONFIRM_ONCE: the bounce lane loop confirms a walk's closest hit once: 0 off, 1 on, 2 auto
+    int debug_fail_confirm = 0; // MIRT_OPT_DEBUG_FAIL_CONFIRM: test hook, confirmations of pixels % N == 0 fail
     mirt::BuildState* build = nullptr;  // mirt_bvh_build_flat_device's scratch (bvh_device.hip)
     mirt_scene_build_stats scene_stats{};  // of the last mirt_scene_build_device
     bool have_scene_stats = false;
@@ -1531,6 +1628,20 @@ int ensure(void** p, size_t* cap, size_t bytes)
     HIP_TRY(hipMalloc(p, bytes));
     *cap = bytes;
     return MIRT_OK;
+}
+
+// MIRT_OPT_CONFIRM_ONCE in effect for the uploaded scene. Automatic (2): on up
+// to kConfirmOnceLeaves leaves. Measured (MEASUREMENTS.md §D, round 8): at
+// 10k spheres (1080p and 4K) every round is ahead of the parent; at 100k the
+// bounce pass alone and the device-resident frames are ahead too, but the
+// rounds of the frames-in-flight headline scatter -5% .. +5% around it (31.7%
+// of the wave's loop iterations hold a confirmation at 10k, 15.2% at 100k).
+// The line is the geometric middle of the two measured sizes; nothing in
+// between has been measured.
+constexpr uint32_t kConfirmOnceLeaves = 1u << 15;
+static bool confirm_once(const mirt_ctx* c)
+{
+    return c->confirm_once == 1 || (c->confirm_once == 2 && c->num_leaves <= kConfirmOnceLeaves);
 }
 
 // MIRT_OPT_LEAF_BATCH: the bounce walk loads a step's passing leaf spheres
@@ -1829,17 +1940,17 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ph1[ps], s));
         if (d_bdiag && sc.wide)
-            bounce_kernel<true, 2, true><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, d_bdiag);
+            bounce_kernel<true, 2, true><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm, d_bdiag);
         else if (d_bdiag)
-            bounce_kernel<true, 0, true><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, d_bdiag);
+            bounce_kernel<true, 0, true><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm, d_bdiag);
         else if (sc.wide && leaf_batch(c))
-            bounce_kernel<true, 4><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain);
+            bounce_kernel<true, 4><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm);
         else if (sc.wide)
-            bounce_kernel<true, 2><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain);
+            bounce_kernel<true, 2><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm);
         else if (c->fast_slab)
-            bounce_kernel<true, 0><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain);
+            bounce_kernel<true, 0><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm);
         else
-            bounce_kernel<false, 0><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain);
+            bounce_kernel<false, 0><<<bblocks, 256, blds, s>>>(sc, f, d_out, d_acc, queue, qctl, c->bounce_threshold, c->quad_drain, confirm_once(c) ? 0 : kExactWalk, c->debug_fail_confirm);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ph2[ps], s));
         if (int rc = fold()) return rc;
@@ -2547,7 +2658,6 @@ int mirt_bounce_stats(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc
     }
     const int waves = (c->bounce_blocks_opt ? c->bounce_blocks_opt : c->bounce_blocks) * 4;
     if (!out || cap < waves) return -waves;
-    static_assert(kBounceDiag == 12, "mirt.h documents 12 words per wave");
     FrameConst f = make_frame_const(cam, fd);
     f.accumulate = 0;
     const size_t pixels = (size_t)f.num_rows * f.width;
@@ -2992,6 +3102,14 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         if (value < 0 || value > 10000) break;
         c->debug_stall_ms = value;
         return MIRT_OK;
+    case MIRT_OPT_CONFIRM_ONCE:
+        if (value < 0 || value > 2) break;
+        c->confirm_once = value;
+        return MIRT_OK;
+    case MIRT_OPT_DEBUG_FAIL_CONFIRM:
+        if (value < 0) break;
+        c->debug_fail_confirm = value;
+        return MIRT_OK;
     case MIRT_OPT_QUEUE_ORDER:
         if (value < 0 || value > 2) break;
         c->queue_order = value;
@@ -3027,6 +3145,8 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_ZERO_COPY) return c->zero_copy;
     if (option == MIRT_OPT_QUEUE_ORDER) return c->queue_order;
     if (option == MIRT_OPT_DEBUG_STALL_MS) return c->debug_stall_ms;
+    if (option == MIRT_OPT_CONFIRM_ONCE) return confirm_once(c) ? 1 : 0;  // in effect for the uploaded scene
+    if (option == MIRT_OPT_DEBUG_FAIL_CONFIRM) return c->debug_fail_confirm;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
     set_error("mirt_get_option: bad option %d", option);
     return MIRT_E_INVALID;

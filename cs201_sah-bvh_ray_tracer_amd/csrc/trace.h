@@ -458,8 +458,9 @@ __device__ __forceinline__ SphRay sph_ray(const Ray& r) { return {r.ox, r.oy, r.
 // 1/(2a) below the normal range 0: the first turns t' - M and t' + M into NaN,
 // which decide nothing; the second needs |b| > 2^105 for a t above EPS, where
 // b b overflows and disc is inf or NaN -- NaN again, or the miss hit.c sees.)
+// `exact` (instrumented builds only): set when the f64 path ran.
 template <bool FAST>
-__device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best)
+__device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best, bool* exact = nullptr)
 {
     const float ocx = r.ox - s.x, ocy = r.oy - s.y, ocz = r.oz - s.z;
     const float b = 2.0f * dot3(ocx, ocy, ocz, r.dx, r.dy, r.dz);
@@ -473,6 +474,7 @@ __device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best)
         if ((te - m > best || te + m <= kEps) && disc >= 0x1p-126f) return -1.0f;
     }
     // hit.c:28 in double: (-b - sqrt(disc)) / (2a), rounded to float
+    if (exact) *exact = true;
     const double num = (double)(-b) - __dsqrt_rn((double)disc);
     const float t = (float)__ddiv_rn(num, r.a2());
     return (t > kEps && t <= best) ? t : -1.0f;
@@ -914,6 +916,32 @@ __device__ __forceinline__ void cx(float& ka, uint32_t& ra, float& kb, uint32_t&
 __device__ __forceinline__ float h_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu)); }
 __device__ __forceinline__ float h_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
 
+// GateDiag (mirt_bounce_stats): how often the timed gate's CONFIRMATION of a
+// candidate runs -- the f64 t of sphere_t (`t`) and the LeafBox loads with
+// the exact box test (`box`). Per lane: the gate executions this lane led
+// (first active lane of the gate loop's iteration: summed over the wave they
+// are the wave's executions) and the confirmations it entered itself; st_*:
+// whether this lane entered one in the current step (reset by the caller).
+struct GateDiag {
+    uint32_t gates, gates_t, gates_box, lanes_t, lanes_box;
+    bool st_gate, st_t, st_box;
+    __device__ __forceinline__ void gate(bool et, bool eb)
+    {
+        const uint64_t act = __ballot(true);
+        const bool lead =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u)) == 0;
+        const bool any_t = __ballot(et) != 0, any_box = __ballot(eb) != 0;
+        gates += lead ? 1u : 0u;
+        gates_t += (lead && any_t) ? 1u : 0u;
+        gates_box += (lead && any_box) ? 1u : 0u;
+        lanes_t += et ? 1u : 0u;
+        lanes_box += eb ? 1u : 0u;
+        st_gate = true;
+        st_t = st_t || et;
+        st_box = st_box || eb;
+    }
+};
+
 // The leaf gate of a leaf slot whose fp16 box passed: its exact box under
 // hit.c's test, then its sphere. COUNT: the sphere test counts.
 //
@@ -922,9 +950,12 @@ __device__ __forceinline__ float h_hi(uint32_t v) { return (float)__builtin_bit_
 // record's 48 B) only for a winning hit -- rare: most gates end at the
 // sphere. Same box test, same prune state, same result; COUNT keeps the
 // reference's order so the box-gated sphere tests are what it counts.
+// et / eb (instrumented builds only): set when the timed order ran the f64 t
+// / loaded the LeafBox.
 template <bool FAST, bool COUNT>
 __device__ __forceinline__ void wide_leaf(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr,
-                                          uint32_t ref, float& best_t, int& best_s, Counters& cnt)
+                                          uint32_t ref, float& best_t, int& best_s, Counters& cnt,
+                                          bool* et = nullptr, bool* eb = nullptr)
 {
     const uint32_t li = ref & ~kPLeaf;
     const float4* lp = (const float4*)(sc.leaf_box + li);
@@ -936,8 +967,9 @@ __device__ __forceinline__ void wide_leaf(const DevScene& sc, const SlabRay& sr,
             consider_sphere<FAST>(sc, sp, pr, sr.ox, sr.oy, sr.oz, __float_as_int(l1.z), g, best_t, best_s);
         }
     } else {
-        const float t = sphere_t<FAST>(sp, sc.leaf_geo[li], best_t);
+        const float t = sphere_t<FAST>(sp, sc.leaf_geo[li], best_t, et);
         if (t > 0.0f) {
+            if (eb) *eb = true;
             const float4 l0 = lp[0], l1 = lp[1];
             const int si = __float_as_int(l1.z);
             if ((t < best_t || si > best_s) && slab_box<FAST>(sr, pr, l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, e)) {
@@ -947,6 +979,77 @@ __device__ __forceinline__ void wide_leaf(const DevScene& sc, const SlabRay& sr,
             }
         }
     }
+}
+
+// The closest hit confirmed ONCE PER WALK (the bounce kernel's lane loop,
+// MIRT_OPT_CONFIRM_ONCE): the gate above reads the candidate's LeafBox and
+// runs hit.c's box test for every hit that could win -- per lane that is
+// rare, but a third of the wave's loop iterations hold such a lane and pay
+// the box code and a third dependent load round trip for one or two of them
+// (MEASUREMENTS.md §D, round 8). A DEFERRED walk accepts a candidate with
+// t < best tentatively -- best_t = t, best_s = the LEAF index, pruning from t
+// -- and tests only the walk's winner against its exact box, with pruning
+// off, when the level is shaded (confirm_leaf). An exact tie loads the two
+// leaves' sphere indices: the larger wins, as above.
+//
+// Why the result is the same. The answer is the least t, a tie to the larger
+// sphere index, among the sphere hits whose exact box passes. The deferred
+// walk finds that least (t, index) among ALL sphere hits of the leaves it
+// reaches; if the winner's box passes it is also the least of the subset. A
+// tentative candidate whose box would fail can only have shut out hits that
+// lose to it, and every later winner beats it, so beats them too; a box is
+// pruned only when every hit in it has t above the best held then, which the
+// same argument covers. If the winner's box FAILS nothing is assumed: the
+// lane sets kExactWalk and walks the level again with the gate above, which
+// confirms every candidate at once and so cannot fail -- a level is walked at
+// most twice. The DFS-segment fallback records sphere indices (lane_step), so
+// a deferred lane that would enter it restarts in exact mode as well.
+constexpr int kExactWalk = 0x100;  // in the lane's `level` word (levels are <= kMaxDepth)
+
+// One leaf gate of the lane loop: `exact` selects the gate above (best_s a
+// sphere index), else the deferred form (best_s a leaf index).
+__device__ __forceinline__ void wide_leaf_once(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr,
+                                               uint32_t ref, bool exact, float& best_t, int& best_s,
+                                               bool* et = nullptr, bool* eb = nullptr)
+{
+    const uint32_t li = ref & ~kPLeaf;
+    const float t = sphere_t<true>(sp, sc.leaf_geo[li], best_t, et);
+    if (t > 0.0f) {
+        // (the two forms side by side, not nested: the walk loop's scalar
+        // registers hold one exec mask per level of nesting)
+        bool win = t < best_t || best_s < 0;  // (t = best = +inf with no hit yet: accepted, as above)
+        int ns = (int)li;
+        float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), l1 = l0;
+        if (exact) {
+            if (eb) *eb = true;
+            const float4* lp = (const float4*)(sc.leaf_box + li);
+            l0 = lp[0];
+            l1 = lp[1];
+            ns = __float_as_int(l1.z);
+            win = t < best_t || ns > best_s;
+        } else if (!win) {  // an exact tie
+            if (eb) *eb = true;
+            win = sc.leaf_box[li].sphere > sc.leaf_box[best_s].sphere;
+        }
+        float e;
+        if (exact && win) win = slab_box<true>(sr, pr, l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, e);
+        if (win) {
+            best_t = t;
+            best_s = ns;
+            if (sc.prune) prune_update(pr, sc, sr.ox, sr.oy, sr.oz, sp.a4(), t);
+        }
+    }
+}
+
+// The confirmation of a deferred walk's winner (leaf `li`): hit.c's box test
+// on its exact box with pruning off. Returns its sphere index, or -1 when
+// the box fails.
+__device__ __forceinline__ int confirm_leaf(const DevScene& sc, const SlabRay& sr, int li)
+{
+    const float4* lp = (const float4*)(sc.leaf_box + li);
+    const float4 l0 = lp[0], l1 = lp[1];
+    float e;
+    return slab_box<true>(sr, prune_off(), l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, e) ? __float_as_int(l1.z) : -1;
 }
 
 // The timed gate of wide_leaf with its sphere already loaded: the sphere,
@@ -972,11 +1075,16 @@ __device__ __forceinline__ void leaf_gate(const DevScene& sc, const SlabRay& sr,
 // every ray) staged in LDS by the caller; a node there is read from LDS
 // instead of through the vector-memory path (the bounce kernel's busiest
 // unit, TD: its cost is the bytes returned per lane, however coalesced).
-template <bool FAST, bool COUNT, bool BATCH = false, bool BND = false>
+// GD (instrumented bounce kernel): the non-batch gate loop reports to `gd`.
+// DEFER (the bounce kernel's lane loop, FAST && !COUNT && !BATCH): the gates
+// are wide_leaf_once, deferred unless *lvl holds kExactWalk.
+template <bool FAST, bool COUNT, bool BATCH = false, bool BND = false, bool GD = false, bool DEFER = false>
 __device__ __forceinline__ void wide_lane_step(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr,
                                                WideWalk& w, uint32_t* stk, float& best_t, int& best_s, Counters& cnt,
-                                               lds_uint4* hc = nullptr, uint32_t hc_n = 0)
+                                               lds_uint4* hc = nullptr, uint32_t hc_n = 0, GateDiag* gd = nullptr,
+                                               int* lvl = nullptr)
 {
+    static_assert(!DEFER || (FAST && !COUNT && !BATCH), "the deferred gates are the timed lane loop's");
     if (COUNT) cnt.steps++;
     if (w.end) {
         lane_step<FAST, COUNT, true>(sc, sr, sp, pr, w.cur, best_t, best_s, cnt);
@@ -1031,10 +1139,25 @@ __device__ __forceinline__ void wide_lane_step(const DevScene& sc, const SlabRay
     if (n == 0) {
         wide_walk_pop(w, stk);
     } else if (w.top + n - 1 > (uint32_t)kWideStack) {
-        // the node's whole subtree as a flat DFS segment, its leaf slots included
-        const HAux ax = sc.haux[w.cur];
-        w.cur = ax.flat + 1;
-        w.end = ax.end;
+        bool segment = true;
+        if constexpr (DEFER) {
+            if (!(*lvl & kExactWalk)) {
+                // a deferred walk holds a leaf index where the segment's gates
+                // hold a sphere index: the level again, in exact mode
+                *lvl |= kExactWalk;
+                w = WideWalk{sc.wide_root, 0u, 0u};
+                best_t = INFINITY;
+                best_s = -1;
+                pr = prune_off();
+                segment = false;
+            }
+        }
+        if (segment) {
+            // the node's whole subtree as a flat DFS segment, its leaf slots included
+            const HAux ax = sc.haux[w.cur];
+            w.cur = ax.flat + 1;
+            w.end = ax.end;
+        }
         lm = 0;
     } else {
         // failing slots get +inf keys and passing ones a finite key, so the n
@@ -1077,12 +1200,21 @@ __device__ __forceinline__ void wide_lane_step(const DevScene& sc, const SlabRay
         }
     } else {
         while (__ballot(lm != 0)) {
+            bool et = false, eb = false;
             if (lm) {
                 const uint32_t i = __builtin_ctz(lm);
                 lm &= lm - 1;
                 const uint32_t ref = i == 0 ? q3.x : i == 1 ? q3.y : i == 2 ? q3.z : q3.w;
-                wide_leaf<FAST, COUNT>(sc, sr, sp, pr, ref, best_t, best_s, cnt);
+                if constexpr (DEFER && GD)
+                    wide_leaf_once(sc, sr, sp, pr, ref, (*lvl & kExactWalk) != 0, best_t, best_s, &et, &eb);
+                else if constexpr (DEFER)
+                    wide_leaf_once(sc, sr, sp, pr, ref, (*lvl & kExactWalk) != 0, best_t, best_s);
+                else if constexpr (GD)
+                    wide_leaf<FAST, COUNT>(sc, sr, sp, pr, ref, best_t, best_s, cnt, &et, &eb);
+                else
+                    wide_leaf<FAST, COUNT>(sc, sr, sp, pr, ref, best_t, best_s, cnt);
             }
+            if constexpr (GD) gd->gate(et, eb);
         }
     }
 }
@@ -1131,7 +1263,8 @@ __device__ __forceinline__ void cand_merge(float& t, int& si)
 template <bool FAST, int STRIDE, int CAP, bool BND = false>
 __device__ __forceinline__ void quad_step(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr,
                                           QuadWalk& w, uint32_t* stk, float& best_t, int& best_s,
-                                          lds_uint4* hc = nullptr, uint32_t hc_n = 0)
+                                          lds_uint4* hc = nullptr, uint32_t hc_n = 0,
+                                          uint32_t lane = threadIdx.x & 63)
 {
     Counters cnt{0, 0, 0, 0, 0};
     if (w.end) {  // DFS segment (the stack was full): every lane of the quad walks it alike
@@ -1147,7 +1280,7 @@ __device__ __forceinline__ void quad_step(const DevScene& sc, const SlabRay& sr,
         }
         return;
     }
-    const uint32_t j = threadIdx.x & 3;
+    const uint32_t j = lane & 3;
     uint4 q;
     if (w.cur < hc_n)
         q = lds_load(hc + 4 * w.cur + j);
@@ -1187,7 +1320,7 @@ __device__ __forceinline__ void quad_step(const DevScene& sc, const SlabRay& sr,
     const uint32_t rank = (uint32_t)(k1 < key || (k1 == key && (j ^ 1) < j)) +
                           (uint32_t)(k2 < key || (k2 == key && (j ^ 2) < j)) +
                           (uint32_t)(k3 < key || (k3 == key && (j ^ 3) < j));
-    const uint32_t n = (uint32_t)__popcll((__ballot(inner) >> (threadIdx.x & 60)) & 0xF);
+    const uint32_t n = (uint32_t)__popcll((__ballot(inner) >> (lane & 60)) & 0xF);
     uint32_t nx = inner && rank == 0 ? q.w + 1 : 0u;  // + 1: 0 means none
     nx |= quad_perm<kQuadXor1>(nx);
     nx |= quad_perm<kQuadXor2>(nx);
@@ -1240,9 +1373,9 @@ __device__ __forceinline__ uint32_t* solo_slot(uint32_t* wst, uint32_t k)
 template <bool FAST, int CAP, bool BND = false>
 __device__ __forceinline__ bool solo_step(const DevScene& sc, const SlabRay& sr, const SphRay& sp, Prune& pr,
                                           SoloWalk& w, uint32_t* wst, float& best_t, int& best_s, lds_uint4* hc,
-                                          uint32_t hc_n)
+                                          uint32_t hc_n, uint32_t lane = threadIdx.x & 63)
 {
-    const uint32_t lane = threadIdx.x & 63, j = lane & 3;
+    const uint32_t j = lane & 3;
     // 1. idle quads take the stack's top entries (quad of idle rank r: entry top - 1 - r)
     const uint64_t idle = __ballot(w.cur == kPNone && j == 0);
     const uint32_t take = min((uint32_t)__popcll(idle), w.top);
@@ -1567,9 +1700,8 @@ __device__ __forceinline__ bool hemisphere_try(uint64_t key, uint32_t k, float& 
 // reached: 0.476^4096), and a lane still pending keeps its latest own try.
 constexpr int kHemisphereRounds = 4096;
 __device__ __forceinline__ void hemisphere_wave(uint64_t key, uint32_t& k, const float* n, bool need, float& x,
-                                                float& y, float& z)
+                                                float& y, float& z, uint32_t lane = threadIdx.x & 63)
 {
-    const uint32_t lane = threadIdx.x & 63;
     bool open = false;  // samples, and no try accepted yet
     if (need) {
         open = !hemisphere_try(key, k, x, y, z);

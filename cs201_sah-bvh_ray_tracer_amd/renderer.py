@@ -437,12 +437,14 @@ class Renderer:
         walking lanes summed, iterations after the queue ran dry, their lanes,
         t_start, t_dry, t_end [10 ns ticks], longest chain << 32 | longest walk,
         quad-drain iterations, t_quad_start, DFS-segment fallback lane-steps,
-        fallbacks entered)."""
+        fallbacks entered, gate executions, those with an f64 t, its lanes, those
+        with a LeafBox load, its lanes, iterations with a gate / f64 t / LeafBox,
+        closest hits confirmed, confirmations failed, fallback restarts)."""
         fd = frame_desc(width, height, depth, True, seed, sample, False, 1, 8, shard, num_shards)
         n = -self.L.mirt_bounce_stats(self.h, C.byref(cam), C.byref(fd), None, 0)
         if n <= 0:
             check(-n, "mirt_bounce_stats")
-        out = np.zeros((n, 12), np.uint64)
+        out = np.zeros((n, abi.BOUNCE_STATS_WORDS), np.uint64)
         check(self.L.mirt_bounce_stats(self.h, C.byref(cam), C.byref(fd), ptr(out), n), "mirt_bounce_stats")
         return out
 

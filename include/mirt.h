@@ -501,15 +501,25 @@ int mirt_count_frame(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_des
 int mirt_wave_stats(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd, uint32_t *out, int cap);
 
 /* Diagnostic: renders the frame (depth >= 2, BVH, wavefront schedule) with the
-   instrumented bounce kernel and writes 12 uint64 per bounce wave: loop
+   instrumented bounce kernel and writes MIRT_BOUNCE_STATS_WORDS uint64 per bounce wave
+   (size `out` from that constant: the record has grown between releases): loop
    iterations, walking lanes summed over them, the same two after the bounce
    queue ran dry, start / queue-dry / end time (100 MHz clock), longest
    chain << 32 | longest walk (steps) of the lane loop, quad-drain loop
    iterations, the time the quad drain began (0: none), lane-steps of the
    lane loop spent in DFS-segment fallbacks (a four-wide step whose pushes
    would overflow the LDS lane stack walks the node's subtree in DFS order)
-   and the fallbacks entered. Returns the number of waves (or -waves if cap
-   is too small). */
+   and the fallbacks entered; then, of the lane loop's leaf gates (the
+   four-wide walk without leaf batching): gate executions (iterations of the
+   per-step gate loop), the executions in which any lane ran the f64 t of a
+   candidate, the lanes that did, the executions in which any lane loaded a
+   LeafBox for the exact box test, the lanes that did, and the loop
+   iterations that held a gate / an f64 t / a LeafBox load; then
+   (MIRT_OPT_CONFIRM_ONCE) the closest hits confirmed, the confirmations that
+   failed (each walks its level again) and the walks restarted because they
+   would have entered a DFS-segment fallback. Returns the
+   number of waves (or -waves if cap is too small). */
+#define MIRT_BOUNCE_STATS_WORDS 23
 int mirt_bounce_stats(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd, uint64_t *out, int cap);
 
 /* The ctx's own stream (a hipStream_t, non-blocking): the blocking calls run
@@ -585,7 +595,20 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
        MIRT_OPT_DEBUG_STALL_MS = 19, /* test hook: every frame of this context starts behind a
                                        kernel that waits this many ms (0..10000, default 0), then
                                        exits -- a frame that overruns a caller's deadline
-                                       (mirt_multi's MIRT_MULTI_OPT_TIMEOUT_MS) without a hang */ };
+                                       (mirt_multi's MIRT_MULTI_OPT_TIMEOUT_MS) without a hang */
+       MIRT_OPT_CONFIRM_ONCE = 21,  /* four-wide bounce walk without leaf batching: 1 = a walk
+                                       tests only its closest sphere hit against the leaf's exact
+                                       box, once, when the level is shaded, and walks the level
+                                       again the old way should that box fail; 0 = every
+                                       candidate hit is tested at once; 2 (default) = 1 for a
+                                       tree of at most 32,768 leaves (measured ahead at 10k
+                                       spheres, not separable at 100k), else 0.
+                                       mirt_get_option reads back 0/1: in effect for the scene.
+                                       Speed only. */
+       MIRT_OPT_DEBUG_FAIL_CONFIRM = 22 /* test hook: N > 0 = that one test reports failure for
+                                       every chain whose pixel index is a multiple of N although
+                                       the box passed, so the second walk runs on ordinary
+                                       scenes (same frames, slower); 0 (default) = off */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back

@@ -22,12 +22,15 @@ def main():
     ap.add_argument("--threshold", type=int, default=20)
     ap.add_argument("--dump", default=None, help="save the raw per-wave records (.npy)")
     ap.add_argument("--shards", default="1", help="comma list: shard 0 of N for each N")
+    ap.add_argument("--confirm-once", type=int, default=2,
+                    help="MIRT_OPT_CONFIRM_ONCE (0: every candidate confirmed at once, 1: once per walk, 2: by tree size)")
     a = ap.parse_args()
     s = mirt.create_random_spheres(a.spheres, 1)
     b = mirt.build_bvh(s)
     r = mirt.Renderer(0)
     r.upload(s, b)
     r.set_option(mirt.abi.OPT_BOUNCE_THRESHOLD, a.threshold)
+    r.set_option(mirt.abi.OPT_CONFIRM_ONCE, a.confirm_once)
     cam = mirt.default_camera()
     for ns in [int(v) for v in a.shards.split(",")]:
         report(r, cam, ns, a)
@@ -61,6 +64,25 @@ def report(r, cam, ns, a):
         "lane_steps": int(d[:, 1].sum()),
         "fallback_lane_steps": int(d[:, 10].sum()), "fallbacks": int(d[:, 11].sum()),
         "fallback_share_of_lane_steps": round(float(d[:, 10].sum() / max(1.0, d[:, 1].sum())), 4),
+        # the confirmation of candidate hits in the lane loop's leaf gates: the
+        # f64 t (sphere_t's exact path) and the LeafBox loads + exact box test
+        "gate_execs": int(d[:, 12].sum()),
+        "gate_execs_per_iter": round(float(d[:, 12].sum() / d[:, 0].sum()), 3),
+        "gate_execs_with_f64_t": int(d[:, 13].sum()), "lanes_f64_t": int(d[:, 14].sum()),
+        "gate_execs_with_leafbox": int(d[:, 15].sum()), "lanes_leafbox": int(d[:, 16].sum()),
+        "share_of_gate_execs_with_f64_t": round(float(d[:, 13].sum() / max(1.0, d[:, 12].sum())), 4),
+        "share_of_gate_execs_with_leafbox": round(float(d[:, 15].sum() / max(1.0, d[:, 12].sum())), 4),
+        "lanes_per_f64_t_exec": round(float(d[:, 14].sum() / max(1.0, d[:, 13].sum())), 2),
+        "lanes_per_leafbox_exec": round(float(d[:, 16].sum() / max(1.0, d[:, 15].sum())), 2),
+        "share_of_iters_with_gate": round(float(d[:, 17].sum() / d[:, 0].sum()), 4),
+        "share_of_iters_with_f64_t": round(float(d[:, 18].sum() / d[:, 0].sum()), 4),
+        "share_of_iters_with_leafbox": round(float(d[:, 19].sum() / d[:, 0].sum()), 4),
+        "share_of_lane_steps_f64_t": round(float(d[:, 14].sum() / max(1.0, d[:, 1].sum())), 5),
+        "share_of_lane_steps_leafbox": round(float(d[:, 16].sum() / max(1.0, d[:, 1].sum())), 5),
+        # MIRT_OPT_CONFIRM_ONCE: closest hits confirmed when shaded, those that failed
+        # (the level is walked again), walks restarted for a DFS-segment fallback
+        "confirmed": int(d[:, 20].sum()), "confirm_failed": int(d[:, 21].sum()),
+        "fallback_restarts": int(d[:, 22].sum()),
         "longest_walk_p50": int(np.median(walk)), "longest_walk_max": int(walk.max()),
         "longest_chain_p50": int(np.median(chain)), "longest_chain_max": int(chain.max())}), flush=True)
 
