@@ -115,6 +115,12 @@ class SceneBuildStats(C.Structure):
                 ("build_ms", C.c_float), ("layout_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class RefitStats(C.Structure):
+    """mirt_refit_stats"""
+    _fields_ = [("on_device", C.c_int32), ("nodes", C.c_int32),
+                ("refit_ms", C.c_float), ("layout_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 class SceneLayoutInfo(C.Structure):
     """mirt_scene_layout_info"""
     _fields_ = [("encloses", C.c_int32), ("ordered", C.c_int32), ("leaf_big", C.c_int32),
@@ -185,6 +191,10 @@ SIGNATURES = [
     ("mirt_scene_upload_flat_device", I, [P, P, I, P, I]),
     ("mirt_last_scene_build_stats", I, [P, P]),
     ("mirt_scene_resident_layout", C.c_int64, [P, I, P, C.c_size_t, P]),
+    ("mirt_bvh_refit_flat", I, [P, I, P, I, I]),
+    ("mirt_scene_refit_device", I, [P, P, I, I, P]),
+    ("mirt_scene_refit_device_ptr", I, [P, P, I, I, P]),
+    ("mirt_last_refit_stats", I, [P, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),

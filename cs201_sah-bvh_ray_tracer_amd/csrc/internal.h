@@ -5,6 +5,8 @@
 
 #include "../../include/mirt.h"
 
+struct ihipStream_t;  // hipStream_t is a pointer to it
+
 namespace mirt {
 
 // Thread-local last error (mirt_last_error()).
@@ -70,6 +72,22 @@ struct DeviceScene {
 // new one is in place), then takes the pointers and scalars.
 int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc);
 void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st);
+// What a refit reads of the resident scene (refit_device.hip): the public 32-B
+// tree and the node depths on the device, and the scalars. false: no scene.
+struct ResidentScene {
+    const mirt_node* nodes32;
+    const uint8_t* ndepth;
+    int num_nodes, num_spheres;
+    bool ordered;
+};
+bool ctx_resident_scene(const mirt_ctx* c, ResidentScene* out);
+void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st);
+// scene_device.hip: the layouts of the `ns` 20-byte spheres at d_aos and the
+// validated flat tree d_nodes[nn], both on the device, made by the layout
+// kernels on `stream` (a hipStream_t) and installed in the ctx. Blocking; on
+// failure the ctx keeps the scene it had.
+int layout_device(mirt_ctx* c, ihipStream_t* stream, const uint32_t* d_aos, int ns, const mirt_node* d_nodes, int nn,
+                  const char* fn);
 // [p, p + bytes) is ONE page-locked host range (mirt_host_alloc /
 // mirt_host_register): copies into it are DMA, asynchronous to the host.
 bool host_page_locked(const void* p, size_t bytes);

@@ -1,0 +1,358 @@
+// Refit of a resident scene on the device (mirt_scene_refit_device[_ptr]): the
+// boxes of the resident 32-B tree recomputed from moved spheres into a scratch
+// tree, by the definition bvh_refit.cpp states on the host, then the device
+// layouts derived again by scene_device.hip's layout_device and installed.
+//
+//   mark     per node: the node copied to the scratch tree (dead leaves keep
+//            their bytes, sphere and skip never change); a hit-able leaf marks
+//            its sphere as the start of a range; the smallest and largest such
+//            sphere and the deepest inner node are reduced into ctl;
+//   spheres  per sphere of [s_0, end): the inputs the kernels decline;
+//   leaves   per hit-able leaf: its range runs from its sphere to the next
+//            marked sphere (or end). A lane folds up to kShort spheres; a longer
+//            range (a stuck group) is queued and folded by one wave, 64 spheres
+//            a step, so a scene of identical spheres costs ns / 64 steps;
+//   levels   one launch per depth, deepest first (design A of DESIGN.md 9.2):
+//            a node's children are one level down, written by the launch
+//            before. The kernel boundary is the only hand-off.
+// The resident scene is `ordered` (else the host refits), so the leaves'
+// spheres increase in pre-order, every mark is set once, and no node is deeper
+// than 62: ndepth is exact. A box is fmin / fmax over finite values none of
+// which is -0.0 (declined), so the order of combination does not show: the
+// host's bits. Every loop is bounded at launch; no workgroup waits on another.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace mirt;
+
+constexpr int kBlock = 256;
+constexpr int kShort = 64;  // spheres a single lane folds before the leaf goes to a wave
+
+// ctl words (device, read back by the host)
+enum {
+    kMinLive = 0,  // smallest / largest sphere of a hit-able leaf (INT_MAX / -1: none)
+    kMaxLive,
+    kMaxDepth,     // depth of the deepest inner node (-1: none)
+    kDeclined,     // a sphere the kernels decline
+    kLong,         // leaves queued for the wave kernel
+    kCtlWords = 8
+};
+
+struct Box {
+    float lo[3], hi[3];
+};
+
+__device__ __forceinline__ Box box_empty()
+{
+    Box b;
+    for (int a = 0; a < 3; a++) {
+        b.lo[a] = __uint_as_float(0x7f800000u);
+        b.hi[a] = __uint_as_float(0xff800000u);
+    }
+    return b;
+}
+
+__device__ __forceinline__ void box_add(Box& b, const uint32_t* aos, int k)
+{
+    const uint32_t* s = aos + 5 * (size_t)k;
+    const float r = __uint_as_float(s[3]);
+    for (int a = 0; a < 3; a++) {
+        const float c = __uint_as_float(s[a]);
+        b.lo[a] = fminf(b.lo[a], c - r);
+        b.hi[a] = fmaxf(b.hi[a], c + r);
+    }
+}
+
+__device__ __forceinline__ bool hitable(const mirt_node& n, int ns)
+{
+    return n.sphere >= 0 && !(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns;
+}
+
+// a child's box into its parent's; a dead leaf contributes the empty box
+__device__ __forceinline__ void box_merge(Box& b, const mirt_node& child, int ns)
+{
+    if (child.sphere >= 0 && !hitable(child, ns)) return;
+    for (int a = 0; a < 3; a++) {
+        b.lo[a] = fminf(b.lo[a], child.bmin[a]);
+        b.hi[a] = fmaxf(b.hi[a], child.bmax[a]);
+    }
+}
+
+__device__ __forceinline__ void store_box(mirt_node* out, int i, const Box& b)
+{
+    for (int a = 0; a < 3; a++) {
+        out[i].bmin[a] = b.lo[a];
+        out[i].bmax[a] = b.hi[a];
+    }
+}
+
+// mark: ns + 1 bytes, zeroed
+__global__ void mark_kernel(const mirt_node* nd, int nn, int ns, const uint8_t* ndepth, mirt_node* out, uint8_t* mark,
+                            int* ctl)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nn) return;
+    const mirt_node n = nd[i];
+    out[i] = n;
+    if (n.sphere < 0) {
+        const int d = ndepth[i];
+        if (d > *(volatile int*)&ctl[kMaxDepth]) atomicMax(&ctl[kMaxDepth], d);
+    } else if (hitable(n, ns)) {
+        mark[n.sphere] = 1;
+        if (n.sphere < *(volatile int*)&ctl[kMinLive]) atomicMin(&ctl[kMinLive], n.sphere);
+        if (n.sphere > *(volatile int*)&ctl[kMaxLive]) atomicMax(&ctl[kMaxLive], n.sphere);
+    }
+}
+
+__global__ void decline_kernel(const uint32_t* aos, int end, int* ctl)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= end || i < ctl[kMinLive]) return;
+    const uint32_t* s = aos + 5 * (size_t)i;
+    bool bad = false;
+    for (int k = 0; k < 4; k++) bad |= (s[k] & 0x7f800000u) == 0x7f800000u;
+    const float r = __uint_as_float(s[3]);
+    for (int a = 0; a < 3; a++) {
+        const float c = __uint_as_float(s[a]);
+        bad |= __float_as_uint(c - r) == 0x80000000u || __float_as_uint(c + r) == 0x80000000u;
+    }
+    if (bad && !*(volatile int*)&ctl[kDeclined]) atomicOr(&ctl[kDeclined], 1);
+}
+
+// queue: nn ints
+__global__ void leaves_kernel(const mirt_node* nd, int nn, int ns, const uint32_t* aos, int end, const uint8_t* mark,
+                              mirt_node* out, int* queue, int* ctl)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nn) return;
+    const mirt_node n = nd[i];
+    if (!hitable(n, ns) || n.sphere >= end) return;  // end <= a leaf's sphere: the host refuses the call
+    Box b = box_empty();
+    int k = n.sphere;
+    for (int step = 0; step < kShort && k < end && (k == n.sphere || !mark[k]); step++, k++) box_add(b, aos, k);
+    if (k < end && !mark[k]) {
+        const int q = atomicAdd(&ctl[kLong], 1);
+        if (q < nn) queue[q] = i;
+        return;
+    }
+    store_box(out, i, b);
+}
+
+// one wave per queued leaf
+__global__ void long_leaves_kernel(const mirt_node* nd, int nn, const uint32_t* aos, int end, const uint8_t* mark,
+                                   mirt_node* out, const int* queue, int count)
+{
+    const int w = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (w >= count) return;
+    const int i = queue[w];
+    if (i < 0 || i >= nn) return;
+    const int first = nd[i].sphere;
+    Box b = box_empty();
+    for (int base = first; base < end; base += 64) {
+        const int k = base + lane;
+        const bool in = k < end && (k == first || !mark[k]);
+        const unsigned long long stop = __ballot(!in);
+        const bool mine = stop ? lane < __builtin_ctzll(stop) : true;
+        if (mine) box_add(b, aos, k);
+        if (stop) break;
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int a = 0; a < 3; a++) {
+            b.lo[a] = fminf(b.lo[a], __shfl_xor(b.lo[a], off));
+            b.hi[a] = fmaxf(b.hi[a], __shfl_xor(b.hi[a], off));
+        }
+    if (lane == 0) store_box(out, i, b);
+}
+
+// the inner nodes of depth d from their children, which the launches before finished
+__global__ void level_kernel(mirt_node* out, int nn, int ns, const uint8_t* ndepth, int d)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nn || ndepth[i] != d || out[i].sphere >= 0 || i + 1 >= nn) return;
+    const mirt_node l = out[i + 1];
+    const uint32_t ri = l.skip & MIRT_SKIP_MASK;
+    if (ri >= (uint32_t)nn) return;
+    const mirt_node r = out[ri];
+    Box b = box_empty();
+    box_merge(b, l, ns);
+    box_merge(b, r, ns);
+    store_box(out, i, b);
+}
+
+// ---- host side
+
+int hip_fail(hipError_t e, const char* what)
+{
+    set_error("%s: %s", what, hipGetErrorString(e));
+    return MIRT_E_DEVICE;
+}
+
+#define HIP_TRY(expr)                                     \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+inline unsigned blocks(size_t items, int per) { return (unsigned)((items + (size_t)per - 1) / (size_t)per); }
+
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// The refit kernels on stream s: d_tree[nn] from the resident tree and the spheres at d_aos. *verdict = 0: d_tree is
+// the refit tree once the stream has run; 1: an input the kernels decline. Blocking (one read-back).
+int refit_kernels(hipStream_t s, const ResidentScene& rs, const uint32_t* d_aos, int end, mirt_node* d_tree,
+                  int* verdict, const char* fn)
+{
+    const int nn = rs.num_nodes, ns = rs.num_spheres;
+    // scratch, one allocation: the ctl words, the queue of long leaves, the range marks
+    const size_t bytes = ((size_t)kCtlWords + (size_t)nn) * 4 + (size_t)ns + 1;
+    DevMem scratch;
+    HIP_TRY(hipMalloc(&scratch.p, bytes));
+    int* ctl = (int*)scratch.p;
+    int* queue = ctl + kCtlWords;
+    uint8_t* mark = (uint8_t*)(queue + nn);
+    int h[kCtlWords] = {};
+    h[kMinLive] = INT_MAX;
+    h[kMaxLive] = h[kMaxDepth] = -1;
+    HIP_TRY(hipMemsetAsync(scratch.p, 0, bytes, s));
+    HIP_TRY(hipMemcpyAsync(ctl, h, sizeof h, hipMemcpyHostToDevice, s));
+    const unsigned gn = blocks((size_t)nn, kBlock);
+    mark_kernel<<<gn, kBlock, 0, s>>>(rs.nodes32, nn, ns, rs.ndepth, d_tree, mark, ctl);
+    if (end > 0) decline_kernel<<<blocks((size_t)end, kBlock), kBlock, 0, s>>>(d_aos, end, ctl);
+    leaves_kernel<<<gn, kBlock, 0, s>>>(rs.nodes32, nn, ns, d_aos, end, mark, d_tree, queue, ctl);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (end <= h[kMaxLive]) {
+        set_error("%s: end %d does not lie behind the last leaf's sphere %d", fn, end, h[kMaxLive]);
+        return MIRT_E_INVALID;
+    }
+    if (h[kLong] < 0 || h[kLong] > nn || h[kMaxDepth] > 62) {
+        set_error("%s: the refit kernels queued %d of %d leaves below depth %d", fn, h[kLong], nn, h[kMaxDepth]);
+        return MIRT_E_DEVICE;
+    }
+    *verdict = h[kDeclined] ? 1 : 0;
+    if (*verdict) return MIRT_OK;
+    if (h[kLong] > 0)
+        long_leaves_kernel<<<blocks((size_t)h[kLong] * 64, kBlock), kBlock, 0, s>>>(rs.nodes32, nn, d_aos, end, mark,
+                                                                                    d_tree, queue, h[kLong]);
+    for (int d = h[kMaxDepth]; d >= 0; d--) level_kernel<<<gn, kBlock, 0, s>>>(d_tree, nn, ns, rs.ndepth, d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));  // the scratch is free again; layout_ms starts behind the kernels
+    return MIRT_OK;
+}
+
+// exactly one of `spheres` (host) and `d_spheres` (device) is set, unless ns == 0
+int refit(mirt_ctx* c, const mirt_sphere* spheres, const void* d_spheres, int ns, int end, mirt_node* out_nodes,
+          const char* fn)
+try {
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (ns < 0 || (ns > 0 && !spheres && !d_spheres) || end < 0 || end > ns) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    ResidentScene rs{};
+    if (!ctx_resident_scene(c, &rs)) {
+        set_error("%s: no scene uploaded", fn);
+        return MIRT_E_NOSCENE;
+    }
+    if (ns != rs.num_spheres) {
+        set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs.num_spheres);
+        return MIRT_E_INVALID;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    const int nn = rs.num_nodes;
+    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns, tree_bytes = sizeof(mirt_node) * (size_t)nn;
+    mirt_refit_stats st{};
+    st.nodes = nn;
+    int declined = nn > 0 && !rs.ordered;
+    if (!declined) {
+        DevMem aos, tree;
+        const uint32_t* d_aos = (const uint32_t*)d_spheres;
+        if (!d_aos) {
+            HIP_TRY(hipMalloc(&aos.p, std::max<size_t>(sph_bytes, 4)));
+            if (ns > 0) HIP_TRY(hipMemcpyAsync(aos.p, spheres, sph_bytes, hipMemcpyHostToDevice, s));
+            d_aos = (const uint32_t*)aos.p;
+        }
+        HIP_TRY(hipMalloc(&tree.p, std::max<size_t>(tree_bytes, sizeof(mirt_node))));
+        int rc = MIRT_OK;
+        if (nn > 0) rc = refit_kernels(s, rs, d_aos, end, (mirt_node*)tree.p, &declined, fn);
+        if (rc || declined) (void)hipStreamSynchronize(s);  // the arrays are freed on the way out
+        if (rc) return rc;
+        if (!declined) {
+            st.refit_ms = since(t0);
+            const auto t1 = std::chrono::steady_clock::now();
+            rc = layout_device(c, s, d_aos, ns, (const mirt_node*)tree.p, nn, fn);
+            hipError_t e = hipSuccess;
+            if (!rc && out_nodes && nn > 0) e = hipMemcpyAsync(out_nodes, tree.p, tree_bytes, hipMemcpyDeviceToHost, s);
+            const hipError_t e2 = hipStreamSynchronize(s);
+            if (rc) return rc;
+            if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, fn);
+            st.layout_ms = since(t1);
+            st.on_device = 1;
+        }
+    }
+    if (declined) {
+        // the host refit and the host upload on the resident tree: the same result
+        std::vector<mirt_sphere> copy;
+        std::vector<mirt_node> nodes((size_t)nn);
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!spheres && ns > 0) {
+            copy.resize((size_t)ns);
+            HIP_TRY(hipMemcpy(copy.data(), d_spheres, sph_bytes, hipMemcpyDeviceToHost));
+            spheres = copy.data();
+        }
+        HIP_TRY(hipMemcpy(nodes.data(), rs.nodes32, tree_bytes, hipMemcpyDeviceToHost));
+        if (int rc = mirt_bvh_refit_flat(nodes.data(), nn, spheres, ns, end)) return rc;
+        if (int rc = mirt_scene_upload_flat(c, spheres, ns, nodes.data(), nn)) return rc;
+        if (out_nodes) std::memcpy(out_nodes, nodes.data(), tree_bytes);
+    }
+    st.total_ms = since(t0);
+    ctx_set_refit_stats(c, st);
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory", fn);
+    return MIRT_E_NOMEM;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mirt_scene_refit_device(mirt_ctx* c, const mirt_sphere* spheres, int num_spheres, int end, mirt_node* out_nodes)
+{
+    return refit(c, spheres, nullptr, num_spheres, end, out_nodes, "mirt_scene_refit_device");
+}
+
+int mirt_scene_refit_device_ptr(mirt_ctx* c, const void* d_spheres, int num_spheres, int end, mirt_node* out_nodes)
+{
+    return refit(c, nullptr, d_spheres, num_spheres, end, out_nodes, "mirt_scene_refit_device_ptr");
+}
+
+}  // extern "C"

@@ -1603,6 +1603,8 @@ struct mirt_ctx {
     mirt::BuildState* build = nullptr;  // mirt_bvh_build_flat_device's scratch (bvh_device.hip)
     mirt_scene_build_stats scene_stats{};  // of the last mirt_scene_build_device
     bool have_scene_stats = false;
+    mirt_refit_stats refit_stats{};  // of the last mirt_scene_refit_device[_ptr]
+    bool have_refit_stats = false;
 };
 
 namespace {
@@ -2211,6 +2213,20 @@ int mirt_last_scene_build_stats(mirt_ctx* c, mirt_scene_build_stats* out)
     return MIRT_OK;
 }
 
+int mirt_last_refit_stats(mirt_ctx* c, mirt_refit_stats* out)
+{
+    if (!c || !out) {
+        set_error("mirt_last_refit_stats: null context or output");
+        return MIRT_E_INVALID;
+    }
+    if (!c->have_refit_stats) {
+        set_error("mirt_last_refit_stats: no mirt_scene_refit_device has finished on this context");
+        return MIRT_E_INVALID;
+    }
+    *out = c->refit_stats;
+    return MIRT_OK;
+}
+
 int mirt_scene_upload(mirt_ctx* c, const mirt_sphere* spheres, int ns, const mirt_bvh_node* root)
 try {
     if (!root) return mirt_scene_upload_flat(c, spheres, ns, nullptr, 0);
@@ -2380,6 +2396,17 @@ void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st)
 {
     c->scene_stats = st;
     c->have_scene_stats = true;
+}
+bool ctx_resident_scene(const mirt_ctx* c, ResidentScene* out)
+{
+    if (c->num_spheres < 0) return false;
+    *out = ResidentScene{c->d_nodes32, c->d_ndepth, c->num_nodes, c->num_spheres, c->ordered_ok};
+    return true;
+}
+void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st)
+{
+    c->refit_stats = st;
+    c->have_refit_stats = true;
 }
 }  // namespace mirt
 

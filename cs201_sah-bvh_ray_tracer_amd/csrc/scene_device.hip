@@ -571,10 +571,12 @@ float bits_float(int b)
     return f;
 }
 
+}  // namespace
+
 // The layouts of the `ns` 20-byte spheres at d_aos and the validated flat tree d_nodes[nn], both on the device,
-// made by the kernels above on stream s and installed in the ctx.
-int layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int ns, const mirt_node* d_nodes, int nn,
-                  const char* fn)
+// made by the kernels above on stream s and installed in the ctx (internal.h: refit_device.hip calls it too).
+int mirt::layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int ns, const mirt_node* d_nodes, int nn,
+                        const char* fn)
 {
     Pending out;
     DeviceScene& sc = out.sc;
@@ -708,8 +710,6 @@ int layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int ns, con
     out.taken = true;
     return MIRT_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

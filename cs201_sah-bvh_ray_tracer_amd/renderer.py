@@ -113,6 +113,22 @@ def validate_bvh(nodes, num_spheres):
           "mirt_bvh_validate_flat")
 
 
+def refit_bvh(tree, spheres, end=None):
+    """mirt_bvh_refit_flat on a copy: the Bvh of `tree` (a Bvh or an abi.NODE
+    array) with every box recomputed bottom-up from `spheres`, which are in the
+    scene's order; sphere and skip of every node stay. `end` is one past the
+    last sphere the tree was built over (default: all of them). Host only.
+    Raises MirtError if the leaves' spheres do not increase in pre-order or
+    `end` does not lie behind the last of them."""
+    spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+    nodes = np.array(tree.nodes if isinstance(tree, Bvh) else tree, dtype=abi.NODE, order="C", copy=True)
+    end = len(spheres) if end is None else end
+    check(load().mirt_bvh_refit_flat(ptr(nodes) if len(nodes) else None, len(nodes),
+                                     ptr(spheres) if len(spheres) else None, len(spheres), end),
+          "mirt_bvh_refit_flat")
+    return Bvh(nodes)
+
+
 def scene_layout(spheres, tree=None):
     """mirt_scene_layout: the device layouts an upload of `spheres` with `tree`
     (a Bvh, an abi.NODE array or None) would send, computed on the host -- no
@@ -361,6 +377,51 @@ class Renderer:
         st = abi.SceneBuildStats()
         check(self.L.mirt_last_scene_build_stats(self.h, C.byref(st)), "mirt_last_scene_build_stats")
         return {k: getattr(st, k) for k, _ in abi.SceneBuildStats._fields_}
+
+    def refit_scene(self, spheres, end=None, return_nodes=False):
+        """Refit the resident scene to `spheres` on the device
+        (mirt_scene_refit_device): the tree's topology stays, its boxes and the
+        device layouts are recomputed, as refit_bvh + upload would leave them.
+        `spheres` holds as many spheres as the resident scene, in its order: a
+        numpy abi.SPHERE array, or a torch tensor on this context's device
+        (uint8, 20 bytes per sphere, contiguous), which is read in place on the
+        context's stream (mirt_scene_refit_device_ptr). `end` is one past the
+        last sphere the tree was built over (default: all). Returns the refit
+        Bvh if return_nodes. last_refit_stats() says how it went."""
+        nodes = None
+        if return_nodes:
+            info = abi.SceneLayoutInfo()
+            size = check(self.L.mirt_scene_resident_layout(self.h, 0, None, 0, C.byref(info)),
+                         "mirt_scene_resident_layout")
+            nodes = np.zeros(size // abi.DNODE.itemsize, abi.NODE)
+        out = ptr(nodes) if nodes is not None and len(nodes) else None
+        if isinstance(spheres, np.ndarray) or not hasattr(spheres, "data_ptr"):
+            spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+            n = len(spheres)
+            end = n if end is None else end
+            check(self.L.mirt_scene_refit_device(self.h, ptr(spheres) if n else None, n, end, out),
+                  "mirt_scene_refit_device")
+        else:
+            nbytes = spheres.numel() * spheres.element_size()
+            if not spheres.is_cuda or spheres.device.index != self.device or not spheres.is_contiguous() \
+                    or nbytes % abi.SPHERE.itemsize:
+                raise MirtError("refit_scene: the tensor must be contiguous, on this context's device and hold "
+                                "20-byte spheres")
+            n = nbytes // abi.SPHERE.itemsize
+            end = n if end is None else end
+            import torch
+            torch.cuda.current_stream(spheres.device).synchronize()  # the tensor's producer: another stream
+            check(self.L.mirt_scene_refit_device_ptr(self.h, C.c_void_p(spheres.data_ptr()) if n else None, n, end,
+                                                     out), "mirt_scene_refit_device_ptr")
+        return Bvh(nodes) if return_nodes else None
+
+    def last_refit_stats(self):
+        """mirt_refit_stats of the last refit_scene on this context, as a dict:
+        on_device (0: input declined, host refit and host upload ran), nodes,
+        refit_ms, layout_ms, total_ms."""
+        st = abi.RefitStats()
+        check(self.L.mirt_last_refit_stats(self.h, C.byref(st)), "mirt_last_refit_stats")
+        return {k: getattr(st, k) for k, _ in abi.RefitStats._fields_}
 
     # ---- frames
     def render_frame(self, cam, width, height, depth=5, use_bvh=True, seed=1, sample=0, accumulate=False,

@@ -288,6 +288,78 @@ typedef struct mirt_scene_build_stats {
 /* Of the ctx's last finished mirt_scene_build_device (MIRT_E_INVALID: none). */
 int mirt_last_scene_build_stats(mirt_ctx *ctx, mirt_scene_build_stats *out);
 
+/* ------------------------------------------ refit: the spheres have moved */
+
+/* Refit nodes[0, num_nodes) in place to `spheres`, which are in the scene's
+   order (the reordered order the build returned): sphere and skip of every
+   node stay, every box is recomputed bottom-up. `end` is one past the last
+   sphere the tree was built over (mirt_bvh_build_flat's end).
+     hit-able leaf  a leaf without MIRT_NODE_EMPTY whose sphere < num_spheres.
+                    Every other leaf is dead and keeps all its bytes.
+     precondition   the hit-able leaves' spheres s_0 < s_1 < ... < s_{k-1}
+                    increase strictly in pre-order and s_{k-1} < end <=
+                    num_spheres (no hit-able leaf: 0 <= end <= num_spheres).
+     leaf box       leaf j's range is [s_j, s_{j+1}), the last leaf's
+                    [s_{k-1}, end) -- the builder's own ranges. Its box is the
+                    empty box (+inf / -inf) folded with fl(c - r), fl(c + r) of
+                    the range's spheres in index order (bvh.c:120-125).
+     inner box      fmin / fmax of the boxes of children i + 1 and skip(i + 1);
+                    a dead leaf contributes the empty box.
+   For a tree the builder made and unchanged spheres the result is the input,
+   bit for bit. What a refit is NOT: the tree the reference would build for the
+   moved spheres -- it would choose new SAH planes. Frames of a refit scene are
+   exactly hit.c:91-109 on the refit tree (ties, leaf gates), not the
+   reference's frame of a rebuilt scene, and the tree's SAH quality decays as
+   the spheres travel: rebuild when it does.
+   The tree is checked as by mirt_bvh_validate_flat, then the precondition;
+   MIRT_E_INVALID leaves `nodes` untouched and mirt_last_error names the first
+   offending node. num_nodes == 0 is MIRT_OK. Never touches the GPU. */
+int mirt_bvh_refit_flat(mirt_node *nodes, int num_nodes, const mirt_sphere *spheres, int num_spheres, int end);
+
+/* Refit the ctx's resident scene to `spheres` (host memory, the scene's order,
+   as many as the resident scene holds) on the device: as if
+   mirt_bvh_refit_flat had run on the resident tree and mirt_scene_upload_flat
+   on its result -- byte for byte the same resident arrays and
+   mirt_scene_layout_info. Kernels (csrc/refit_device.hip) recompute the boxes
+   from the resident 32-B tree into a scratch tree: the leaf boxes, then the
+   inner boxes one launch per depth, deepest first. The device layouts are then
+   derived again by the kernels of mirt_scene_build_device -- they cannot be
+   patched in place: the four-wide layout splits the slot of largest area, so
+   its slot references move with the boxes -- and the new scene is installed.
+   Frames already enqueued finish on the old scene; a failure leaves the old
+   scene installed (for a declined input, whose last step is
+   mirt_scene_upload_flat itself, a failure up to that call does); the
+   accumulation buffer is the caller's to restart, as after an upload. `out_nodes` (may be NULL) receives the refit tree, the
+   resident scene's num_nodes nodes. A resident scene without a tree just gets
+   its spheres replaced.
+   Declined inputs (mirt_refit_stats.on_device = 0) take the resident tree to
+   the host, mirt_bvh_refit_flat and mirt_scene_upload_flat, with the same
+   result: a NaN or infinite centre or radius in [s_0, end); a sphere box
+   coordinate equal to -0.0 (see mirt_bvh_build_flat_device); a resident scene
+   whose `ordered` flag is 0 -- the host refit then decides: a tree that is
+   monotone but deeper than 62 levels is refit there, one that is not monotone
+   is MIRT_E_INVALID.
+   MIRT_E_NOSCENE without a resident scene; MIRT_E_INVALID if num_spheres is
+   not the resident scene's or end is out of range. A NULL ctx or bad
+   arguments are MIRT_E_INVALID before any HIP call. */
+int mirt_scene_refit_device(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres, int end,
+                            mirt_node *out_nodes);
+/* The same with the spheres already on the ctx's device: d_spheres points at
+   num_spheres 20-byte spheres in device memory, read on the ctx's stream (a
+   caller that animates on the GPU). */
+int mirt_scene_refit_device_ptr(mirt_ctx *ctx, const void *d_spheres, int num_spheres, int end,
+                                mirt_node *out_nodes);
+
+typedef struct mirt_refit_stats {
+    int32_t on_device;   /* 1: refit and laid out by the kernels; 0: input declined, host refit + host upload */
+    int32_t nodes;
+    float   refit_ms;    /* host clock over the sphere copy and the refit kernels (0 when on_device == 0) */
+    float   layout_ms;   /* host clock over the layout kernels, their read-backs and allocations (0 likewise) */
+    float   total_ms;    /* call to return, host clock */
+} mirt_refit_stats;
+/* Of the ctx's last finished mirt_scene_refit_device[_ptr] (MIRT_E_INVALID: none). */
+int mirt_last_refit_stats(mirt_ctx *ctx, mirt_refit_stats *out);
+
 /* ---------------------------------------------------------- rendering */
 
 /* Number of rows (and the row indices, if rows != NULL) a shard renders. */

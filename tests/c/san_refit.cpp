@@ -1,0 +1,172 @@
+// The host refit (csrc/bvh_refit.cpp) under the sanitizers:
+// `make -C cs201_sah-bvh_ray_tracer_amd/csrc san_refit` links this driver with
+// bvh_refit.cpp, bvh_build.cpp and host_scene.cpp built
+// -fsanitize=address,undefined (build/san_refit). It drives
+// mirt_bvh_refit_flat on identity, moved and invalid inputs: builder trees with
+// stuck groups and 0-sphere leaves, a tree built over [0, n - 1), trees that
+// index the never-hit sentinel, non-monotone and malformed trees, every bad
+// `end`. Exit 0 = every check held and no sanitizer fired (they abort on a
+// finding).
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/mirt.h"
+
+static int failures = 0;
+#define CHECK(cond)                                                   \
+    do {                                                              \
+        if (!(cond)) {                                                \
+            std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); \
+            failures++;                                               \
+        }                                                             \
+    } while (0)
+
+static std::vector<mirt_sphere> scene(bool bench, int n, unsigned seed)
+{
+    std::vector<mirt_sphere> s((size_t)n);
+    mirt_rand_state st;
+    mirt_srand(&st, seed);
+    if (bench)
+        CHECK(mirt_scene_benchmark(&st, s.data(), n, 1000.0f) == MIRT_OK);
+    else
+        CHECK(mirt_scene_random(&st, s.data(), n) == MIRT_OK);
+    return s;
+}
+
+static std::vector<mirt_node> flat_build(std::vector<mirt_sphere>& s, int start, int end, int depth)
+{
+    mirt_node* nodes = nullptr;
+    int n = 0;
+    CHECK(mirt_bvh_build_flat(s.data(), start, end, depth, &nodes, &n) == MIRT_OK);
+    std::vector<mirt_node> out(nodes, nodes + n);
+    mirt_bvh_free_flat(nodes);
+    return out;
+}
+
+static bool same(const std::vector<mirt_node>& a, const std::vector<mirt_node>& b)
+{
+    return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(mirt_node)) == 0;
+}
+
+// a deterministic shake: centres by up to +-amp, radii by a factor in [0.5, 1.5)
+static std::vector<mirt_sphere> moved(const std::vector<mirt_sphere>& s, float amp, unsigned seed)
+{
+    std::vector<mirt_sphere> out = s;
+    mirt_rand_state st;
+    mirt_srand(&st, seed);
+    auto unit = [&] { return (float)(mirt_rand(&st) % 20001) / 10000.0f - 1.0f; };
+    for (mirt_sphere& p : out) {
+        p.center.x += amp * unit();
+        p.center.y += amp * unit();
+        p.center.z += amp * unit();
+        p.radius *= 1.0f + 0.5f * unit();
+    }
+    return out;
+}
+
+static int refit(std::vector<mirt_node>& nd, const std::vector<mirt_sphere>& s, int end)
+{
+    return mirt_bvh_refit_flat(nd.empty() ? nullptr : nd.data(), (int)nd.size(), s.empty() ? nullptr : s.data(),
+                               (int)s.size(), end);
+}
+
+// identity, there and back, and the boxes nest (validate_flat checks the topology only)
+static void round_trip(std::vector<mirt_sphere> s, int start, int end, int depth)
+{
+    const std::vector<mirt_node> tree = flat_build(s, start, end, depth);
+    const int ns = (int)s.size();
+    std::vector<mirt_node> work = tree;
+    CHECK(refit(work, s, end) == MIRT_OK);
+    CHECK(same(work, tree));
+    for (float amp : {0.05f, 3.0f}) {
+        const std::vector<mirt_sphere> s2 = moved(s, amp, 7);
+        CHECK(refit(work, s2, end) == MIRT_OK);
+        CHECK(!same(work, tree));
+        CHECK(mirt_bvh_validate_flat(work.data(), (int)work.size(), ns) == MIRT_OK);
+        for (size_t i = 0; i < work.size(); i++) {
+            CHECK(work[i].sphere == tree[i].sphere && work[i].skip == tree[i].skip);
+            if (work[i].sphere >= 0) continue;
+            for (uint32_t c : {(uint32_t)i + 1, work[i + 1].skip & MIRT_SKIP_MASK}) {
+                const mirt_node& k = work[c];
+                if (k.sphere >= 0 && ((k.skip & MIRT_NODE_EMPTY) || k.sphere >= ns)) continue;
+                for (int a = 0; a < 3; a++) CHECK(work[i].bmin[a] <= k.bmin[a] && work[i].bmax[a] >= k.bmax[a]);
+            }
+        }
+        CHECK(refit(work, s, end) == MIRT_OK);
+        CHECK(same(work, tree));
+    }
+}
+
+static mirt_node node(int32_t sphere, uint32_t skip)
+{
+    mirt_node n{};
+    n.bmax[0] = n.bmax[1] = n.bmax[2] = 1.0f;
+    n.sphere = sphere;
+    n.skip = skip;
+    return n;
+}
+
+int main()
+{
+    round_trip(scene(false, 1000, 2), 0, 1000, 0);
+    round_trip(scene(false, 10000, 1), 0, 10000, 0);
+    round_trip(scene(true, 1000, 1), 0, 999, 20);       // benchmark.c:317
+    round_trip(scene(true, 40000, 1), 0, 39999, 20);    // the threaded build
+    {
+        std::vector<mirt_sphere> s = scene(false, 64, 5);  // one stuck group of 32
+        for (int i = 9; i < 40; i++) s[(size_t)i] = s[8];
+        round_trip(s, 0, 64, 0);
+        std::vector<mirt_sphere> one(s.begin(), s.begin() + 1);
+        round_trip(one, 0, 1, 0);
+    }
+    const std::vector<mirt_sphere> s = scene(false, 8, 3);
+    {   // every bad `end`, and the tree untouched
+        std::vector<mirt_sphere> b = s;
+        const std::vector<mirt_node> tree = flat_build(b, 0, 8, 0);
+        int last = -1;
+        for (const mirt_node& n : tree)
+            if (n.sphere >= 0 && n.sphere < 8 && !(n.skip & MIRT_NODE_EMPTY)) last = n.sphere;
+        std::vector<mirt_node> work = tree;
+        for (int end : {last, last - 1, 0, -1, 9, 1 << 30}) {
+            CHECK(refit(work, b, end) == MIRT_E_INVALID);
+            CHECK(same(work, tree));
+        }
+        CHECK(std::strstr(mirt_last_error(), "mirt_bvh_refit_flat: end") != nullptr);
+        CHECK(refit(work, b, last + 1) == MIRT_OK);
+        CHECK(mirt_bvh_refit_flat(nullptr, (int)tree.size(), b.data(), 8, 8) == MIRT_E_INVALID);
+        CHECK(mirt_bvh_refit_flat(work.data(), (int)tree.size(), nullptr, 8, 8) == MIRT_E_INVALID);
+        CHECK(mirt_bvh_refit_flat(work.data(), -1, b.data(), 8, 8) == MIRT_E_INVALID);
+        CHECK(mirt_bvh_refit_flat(work.data(), (int)tree.size(), b.data(), -1, 0) == MIRT_E_INVALID);
+    }
+    {   // no tree
+        CHECK(mirt_bvh_refit_flat(nullptr, 0, s.data(), 8, 8) == MIRT_OK);
+        CHECK(mirt_bvh_refit_flat(nullptr, 0, nullptr, 0, 0) == MIRT_OK);
+        CHECK(mirt_bvh_refit_flat(nullptr, 0, s.data(), 8, 9) == MIRT_E_INVALID);
+    }
+    {   // leaf spheres falling in pre-order; a leaf on the never-hit sentinel; a malformed tree
+        std::vector<mirt_node> falling = {node(-1, 3), node(1, 2), node(0, 3)};
+        const std::vector<mirt_node> keep = falling;
+        CHECK(refit(falling, s, 8) == MIRT_E_INVALID);
+        CHECK(std::strstr(mirt_last_error(), "node 2 holds sphere 0 after sphere 1") != nullptr);
+        CHECK(same(falling, keep));
+        std::vector<mirt_node> sentinel = {node(-1, 3), node(2, 2), node(8, 3)};
+        const mirt_node dead = sentinel[2];
+        CHECK(refit(sentinel, s, 8) == MIRT_OK);
+        CHECK(std::memcmp(&sentinel[2], &dead, sizeof dead) == 0);
+        for (int a = 0; a < 3; a++) CHECK(sentinel[0].bmin[a] == sentinel[1].bmin[a]);   // the range [2, 8)
+        std::vector<mirt_node> both_dead = {node(-1, 3), node(8, 2), node(0, 3 | MIRT_NODE_EMPTY)};
+        CHECK(refit(both_dead, s, 0) == MIRT_OK);
+        CHECK(both_dead[0].bmin[0] > both_dead[0].bmax[0]);                             // the empty box
+        std::vector<mirt_node> bad = {node(-1, 3), node(0, 2), node(9, 3)};
+        CHECK(refit(bad, s, 8) == MIRT_E_INVALID);
+        CHECK(std::strstr(mirt_last_error(), "malformed node 2") != nullptr);
+    }
+    if (failures) {
+        std::fprintf(stderr, "san_refit: %d check(s) failed\n", failures);
+        return 1;
+    }
+    std::puts("san_refit: ok");
+    return 0;
+}
