@@ -121,6 +121,19 @@ class RefitStats(C.Structure):
                 ("refit_ms", C.c_float), ("layout_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class TreeQuality(C.Structure):
+    """mirt_tree_quality"""
+    _fields_ = [("inner_area", C.c_double), ("leaf_area", C.c_double), ("overhead", C.c_double), ("cost", C.c_double),
+                ("root_area", C.c_float), ("inner_nodes", C.c_int32), ("leaves", C.c_int32),
+                ("dead_leaves", C.c_int32), ("clamped", C.c_int32), ("degenerate", C.c_int32)]
+
+
+class UpdateResult(C.Structure):
+    """mirt_update_result"""
+    _fields_ = [("rebuilt", C.c_int32), ("on_device", C.c_int32), ("base_cost", C.c_double), ("cost", C.c_double),
+                ("decay", C.c_double), ("installed", TreeQuality), ("total_ms", C.c_float)]
+
+
 class SceneLayoutInfo(C.Structure):
     """mirt_scene_layout_info"""
     _fields_ = [("encloses", C.c_int32), ("ordered", C.c_int32), ("leaf_big", C.c_int32),
@@ -195,6 +208,9 @@ SIGNATURES = [
     ("mirt_scene_refit_device", I, [P, P, I, I, P]),
     ("mirt_scene_refit_device_ptr", I, [P, P, I, I, P]),
     ("mirt_last_refit_stats", I, [P, P]),
+    ("mirt_bvh_quality_flat", I, [P, I, I, P]),
+    ("mirt_scene_quality", I, [P, P]),
+    ("mirt_scene_update_device", I, [P, P, I, I, I, C.c_double, P, P, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),

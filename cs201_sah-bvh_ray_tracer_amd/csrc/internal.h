@@ -88,6 +88,15 @@ void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st);
 // failure the ctx keeps the scene it had.
 int layout_device(mirt_ctx* c, ihipStream_t* stream, const uint32_t* d_aos, int ns, const mirt_node* d_nodes, int nn,
                   const char* fn);
+// quality_device.hip: the mirt_tree_quality of the validated flat tree
+// d_nodes[nn] on the device, by the kernel on `stream`, byte for byte what
+// mirt_bvh_quality_flat gives for those nodes. Blocking; touches no ctx.
+int quality_device(ihipStream_t* stream, const mirt_node* d_nodes, int nn, int ns, mirt_tree_quality* out,
+                   const char* fn);
+// render.hip: the cost of the tree the last mirt_scene_update_device installed
+// (false: none -- every install drops it, only that call sets it again).
+bool ctx_base_cost(const mirt_ctx* c, double* cost);
+void ctx_set_base_cost(mirt_ctx* c, double cost);
 // [p, p + bytes) is ONE page-locked host range (mirt_host_alloc /
 // mirt_host_register): copies into it are DMA, asynchronous to the host.
 bool host_page_locked(const void* p, size_t bytes);

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "quality.h"
 
 #pragma clang fp contract(off)
 
@@ -192,6 +193,17 @@ __global__ void level_kernel(mirt_node* out, int nn, int ns, const uint8_t* ndep
     store_box(out, i, b);
 }
 
+// mirt_scene_update_device's rebuild: the build ran on spheres whose colour word held their index, and the
+// builders never read it. perm[i] = the index that travelled to place i; the sphere's own colour goes back.
+__global__ void perm_kernel(uint32_t* aos, int ns, const uint32_t* colour, int32_t* perm)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= ns) return;
+    const uint32_t from = aos[5 * (size_t)i + 4];
+    perm[i] = (int32_t)from;
+    if (from < (uint32_t)ns) aos[5 * (size_t)i + 4] = colour[from];
+}
+
 // ---- host side
 
 int hip_fail(hipError_t e, const char* what)
@@ -341,9 +353,177 @@ try {
     return MIRT_E_NOMEM;
 }
 
+// the spheres with the colour word of each replaced by its index: what a build is run on to learn its permutation
+std::vector<mirt_sphere> indexed(const mirt_sphere* spheres, int ns)
+{
+    std::vector<mirt_sphere> out(spheres, spheres + ns);
+    for (int32_t i = 0; i < ns; i++) std::memcpy(&out[(size_t)i].color, &i, 4);
+    return out;
+}
+
+void identity(const mirt_sphere* spheres, int ns, mirt_sphere* reordered, int32_t* perm)
+{
+    if (reordered && ns > 0) std::memcpy(reordered, spheres, sizeof(mirt_sphere) * (size_t)ns);
+    if (perm)
+        for (int32_t i = 0; i < ns; i++) perm[i] = i;
+}
+
+// mirt_scene_update_device: refit into the scratch tree, measure it, then install either it or a
+// rebuild. Nothing is installed, and the ctx's base cost is not touched, before the decision's own tree is complete.
+int update(mirt_ctx* c, const mirt_sphere* spheres, int ns, int start, int end, double max_decay,
+           mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
+try {
+    const char* fn = "mirt_scene_update_device";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (ns < 0 || (ns > 0 && !spheres) || start < 0 || end < start || end > ns) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    ResidentScene rs{};
+    if (!ctx_resident_scene(c, &rs)) {
+        set_error("%s: no scene uploaded", fn);
+        return MIRT_E_NOSCENE;
+    }
+    if (ns != rs.num_spheres) {
+        set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs.num_spheres);
+        return MIRT_E_INVALID;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    const int nn = rs.num_nodes;
+    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns, tree_bytes = sizeof(mirt_node) * (size_t)nn;
+    mirt_update_result res;
+    std::memset(&res, 0, sizeof res);
+    double base = 0.0;
+    if (!ctx_base_cost(c, &base)) {  // the resident tree came from another call: its cost is the base
+        mirt_tree_quality q;
+        if (int rc = quality_device(s, rs.nodes32, nn, ns, &q, fn)) return rc;
+        base = q.cost;
+    }
+    res.base_cost = base;
+    double new_base = base;
+    auto wants_rebuild = [&](const mirt_tree_quality& q) {
+        res.cost = q.cost;
+        res.decay = quality_decay(q.cost, base);
+        return max_decay > 0.0 && res.decay > max_decay;
+    };
+    int declined = nn > 0 && !rs.ordered;
+    if (!declined) {
+        DevMem aos, tree;
+        HIP_TRY(hipMalloc(&aos.p, std::max<size_t>(sph_bytes, 4)));
+        if (ns > 0) HIP_TRY(hipMemcpyAsync(aos.p, spheres, sph_bytes, hipMemcpyHostToDevice, s));
+        const uint32_t* d_aos = (const uint32_t*)aos.p;
+        HIP_TRY(hipMalloc(&tree.p, std::max<size_t>(tree_bytes, sizeof(mirt_node))));
+        int rc = MIRT_OK;
+        if (nn > 0) rc = refit_kernels(s, rs, d_aos, end, (mirt_node*)tree.p, &declined, fn);
+        if (rc || declined) (void)hipStreamSynchronize(s);  // the arrays are freed on the way out
+        if (rc) return rc;
+        mirt_tree_quality q;
+        if (!declined && (rc = quality_device(s, (const mirt_node*)tree.p, nn, ns, &q, fn))) return rc;
+        if (!declined && !wants_rebuild(q)) {
+            rc = layout_device(c, s, d_aos, ns, (const mirt_node*)tree.p, nn, fn);
+            const hipError_t e = hipStreamSynchronize(s);
+            if (rc) return rc;
+            if (e != hipSuccess) return hip_fail(e, fn);
+            identity(spheres, ns, reordered, perm);
+            res.installed = q;
+            res.on_device = 1;
+        } else if (!declined) {
+            const std::vector<mirt_sphere> copy = indexed(spheres, ns);
+            ResidentTree built{};
+            if ((rc = build_resident(c, copy.data(), ns, start, end, 0, &built, &declined))) return rc;
+            if (!declined) {
+                // the spheres' own colours, then the permutation: one allocation
+                DevMem extra;
+                std::vector<uint32_t> colour((size_t)ns);
+                for (int i = 0; i < ns; i++) std::memcpy(&colour[(size_t)i], &spheres[i].color, 4);
+                hipError_t e = hipMalloc(&extra.p, std::max<size_t>((size_t)ns * 8, 8));
+                uint32_t* d_colour = (uint32_t*)extra.p;
+                int32_t* d_perm = (int32_t*)(d_colour + ns);
+                if (e == hipSuccess && ns > 0) {
+                    e = hipMemcpyAsync(d_colour, colour.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s);
+                    if (e == hipSuccess) {
+                        perm_kernel<<<blocks((size_t)ns, kBlock), kBlock, 0, s>>>((uint32_t*)built.aos, ns, d_colour,
+                                                                                   d_perm);
+                        e = hipGetLastError();
+                    }
+                }
+                mirt_tree_quality qb;
+                if (e == hipSuccess) rc = quality_device(s, built.nodes, built.num_nodes, ns, &qb, fn);
+                if (e == hipSuccess && !rc) rc = layout_device(c, s, built.aos, ns, built.nodes, built.num_nodes, fn);
+                if (e == hipSuccess && !rc && reordered && ns > 0)
+                    e = hipMemcpyAsync(reordered, built.aos, sph_bytes, hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess && !rc && perm && ns > 0)
+                    e = hipMemcpyAsync(perm, d_perm, (size_t)ns * 4, hipMemcpyDeviceToHost, s);
+                const hipError_t e2 = hipStreamSynchronize(s);  // `copy`, `colour` and `extra` are free again
+                if (rc) return rc;
+                if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, fn);
+                res.rebuilt = 1;
+                res.installed = qb;
+                res.on_device = 1;
+                new_base = qb.cost;
+            } else {
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+    }
+    if (declined) {
+        // the host refit, the host measure, then the host upload or the host build and upload: the same result
+        std::vector<mirt_node> nodes((size_t)nn);
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nn > 0) HIP_TRY(hipMemcpy(nodes.data(), rs.nodes32, tree_bytes, hipMemcpyDeviceToHost));
+        if (int rc = mirt_bvh_refit_flat(nodes.data(), nn, spheres, ns, end)) return rc;
+        mirt_tree_quality q;
+        if (int rc = mirt_bvh_quality_flat(nodes.data(), nn, ns, &q)) return rc;
+        if (!wants_rebuild(q)) {
+            if (int rc = mirt_scene_upload_flat(c, spheres, ns, nodes.data(), nn)) return rc;
+            identity(spheres, ns, reordered, perm);
+            res.installed = q;
+        } else {
+            std::vector<mirt_sphere> copy = indexed(spheres, ns);
+            mirt_node* bn = nullptr;
+            int bcount = 0;
+            if (int rc = mirt_bvh_build_flat(copy.data(), start, end, 0, &bn, &bcount)) return rc;
+            std::vector<int32_t> from((size_t)ns);
+            for (int i = 0; i < ns; i++) {
+                std::memcpy(&from[(size_t)i], &copy[(size_t)i].color, 4);
+                copy[(size_t)i].color = spheres[from[(size_t)i]].color;
+            }
+            mirt_tree_quality qb;
+            int rc = mirt_bvh_quality_flat(bn, bcount, ns, &qb);
+            if (!rc) rc = mirt_scene_upload_flat(c, copy.data(), ns, bn, bcount);
+            mirt_bvh_free_flat(bn);
+            if (rc) return rc;
+            if (reordered && ns > 0) std::memcpy(reordered, copy.data(), sph_bytes);
+            if (perm && ns > 0) std::memcpy(perm, from.data(), (size_t)ns * 4);
+            res.rebuilt = 1;
+            res.installed = qb;
+            new_base = qb.cost;
+        }
+        res.on_device = 0;
+    }
+    ctx_set_base_cost(c, new_base);
+    res.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (out) *out = res;
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("mirt_scene_update_device: out of host memory");
+    return MIRT_E_NOMEM;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mirt_scene_update_device(mirt_ctx* c, const mirt_sphere* spheres, int num_spheres, int start, int end,
+                             double max_decay, mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
+{
+    return update(c, spheres, num_spheres, start, end, max_decay, reordered, perm, out);
+}
 
 int mirt_scene_refit_device(mirt_ctx* c, const mirt_sphere* spheres, int num_spheres, int end, mirt_node* out_nodes)
 {

@@ -1605,6 +1605,8 @@ struct mirt_ctx {
     bool have_scene_stats = false;
     mirt_refit_stats refit_stats{};  // of the last mirt_scene_refit_device[_ptr]
     bool have_refit_stats = false;
+    double base_cost = 0.0;     // mirt_scene_update_device: the cost of the tree it last installed
+    bool have_base_cost = false;  // dropped by every install of a scene
 };
 
 namespace {
@@ -2131,6 +2133,7 @@ try {
             *u.dst = nullptr;
         }
     c->num_spheres = -1;  // until every array is in place ctx_ok rejects the context
+    c->have_base_cost = false;
     auto put = [](void** dst, size_t alloc, size_t off, const void* src, size_t bytes) {
         if (alloc) HIP_TRY(hipMalloc(dst, alloc));
         if (bytes) HIP_TRY(hipMemcpy((char*)*dst + off, src, bytes, hipMemcpyHostToDevice));
@@ -2368,6 +2371,7 @@ int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
         *p = nullptr;
     }
     c->num_spheres = -1;
+    c->have_base_cost = false;
     c->d_nodes = (DNode*)sc.dnodes;
     c->d_nodes32 = (mirt_node*)sc.nodes32;
     c->d_geo = (float4*)sc.geo;
@@ -2407,6 +2411,16 @@ void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st)
 {
     c->refit_stats = st;
     c->have_refit_stats = true;
+}
+bool ctx_base_cost(const mirt_ctx* c, double* cost)
+{
+    if (c->have_base_cost) *cost = c->base_cost;
+    return c->have_base_cost;
+}
+void ctx_set_base_cost(mirt_ctx* c, double cost)
+{
+    c->base_cost = cost;
+    c->have_base_cost = true;
 }
 }  // namespace mirt
 

@@ -129,6 +129,25 @@ def refit_bvh(tree, spheres, end=None):
     return Bvh(nodes)
 
 
+def _fields(st):
+    """A ctypes struct as a dict (nested structs as dicts)."""
+    return {k: _fields(getattr(st, k)) if issubclass(t, C.Structure) else getattr(st, k) for k, t in st._fields_}
+
+
+def bvh_quality(tree, num_spheres):
+    """mirt_bvh_quality_flat: the SAH quality of `tree` (a Bvh or an abi.NODE
+    array) over num_spheres spheres, as a dict of the mirt_tree_quality fields:
+    inner_area / leaf_area (the two sums), overhead (their ratio), cost
+    (0.125 * overhead + 1), root_area, inner_nodes, leaves, dead_leaves,
+    clamped, degenerate. cost over the cost at build time says how far a refit
+    tree has decayed. Host only; raises MirtError for a malformed tree."""
+    nodes = np.ascontiguousarray(tree.nodes if isinstance(tree, Bvh) else tree, dtype=abi.NODE)
+    q = abi.TreeQuality()
+    check(load().mirt_bvh_quality_flat(ptr(nodes) if len(nodes) else None, len(nodes), num_spheres, C.byref(q)),
+          "mirt_bvh_quality_flat")
+    return _fields(q)
+
+
 def scene_layout(spheres, tree=None):
     """mirt_scene_layout: the device layouts an upload of `spheres` with `tree`
     (a Bvh, an abi.NODE array or None) would send, computed on the host -- no
@@ -422,6 +441,33 @@ class Renderer:
         st = abi.RefitStats()
         check(self.L.mirt_last_refit_stats(self.h, C.byref(st)), "mirt_last_refit_stats")
         return {k: getattr(st, k) for k, _ in abi.RefitStats._fields_}
+
+    def scene_quality(self):
+        """mirt_scene_quality: bvh_quality() of the resident tree, measured by
+        a kernel on this context's device; the same dict, bit for bit."""
+        q = abi.TreeQuality()
+        check(self.L.mirt_scene_quality(self.h, C.byref(q)), "mirt_scene_quality")
+        return _fields(q)
+
+    def update_scene(self, spheres, start=0, end=None, max_decay=0.0):
+        """Refit the resident scene to `spheres` (a numpy abi.SPHERE array in
+        the scene's order) and rebuild it instead when the refit tree's cost
+        has grown past max_decay times the cost of the tree the last
+        update_scene installed (mirt_scene_update_device; max_decay <= 0 never
+        rebuilds). Returns (reordered, perm, result): the spheres in the order
+        the scene now holds them, reordered[i] == spheres[perm[i]] (the
+        identity unless rebuilt), and the mirt_update_result fields as a dict
+        (rebuilt, on_device, base_cost, cost, decay, installed, total_ms)."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        n = len(spheres)
+        end = n if end is None else end
+        reordered = np.zeros(n, abi.SPHERE)
+        perm = np.zeros(n, np.int32)
+        res = abi.UpdateResult()
+        check(self.L.mirt_scene_update_device(self.h, ptr(spheres) if n else None, n, start, end, max_decay,
+                                              ptr(reordered) if n else None, ptr(perm) if n else None, C.byref(res)),
+              "mirt_scene_update_device")
+        return reordered, perm, _fields(res)
 
     # ---- frames
     def render_frame(self, cam, width, height, depth=5, use_bvh=True, seed=1, sample=0, accumulate=False,

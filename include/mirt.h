@@ -310,7 +310,8 @@ int mirt_last_scene_build_stats(mirt_ctx *ctx, mirt_scene_build_stats *out);
    moved spheres -- it would choose new SAH planes. Frames of a refit scene are
    exactly hit.c:91-109 on the refit tree (ties, leaf gates), not the
    reference's frame of a rebuilt scene, and the tree's SAH quality decays as
-   the spheres travel: rebuild when it does.
+   the spheres travel: mirt_bvh_quality_flat / mirt_scene_quality measure by
+   how much, and mirt_scene_update_device refits or rebuilds by that measure.
    The tree is checked as by mirt_bvh_validate_flat, then the precondition;
    MIRT_E_INVALID leaves `nodes` untouched and mirt_last_error names the first
    offending node. num_nodes == 0 is MIRT_OK. Never touches the GPU. */
@@ -359,6 +360,90 @@ typedef struct mirt_refit_stats {
 } mirt_refit_stats;
 /* Of the ctx's last finished mirt_scene_refit_device[_ptr] (MIRT_E_INVALID: none). */
 int mirt_last_refit_stats(mirt_ctx *ctx, mirt_refit_stats *out);
+
+/* ------------------------- quality: has the refit tree decayed? */
+
+/* The SAH quality of a flat tree: the area of its inner nodes per unit of area
+   of its hit-able leaves (a leaf without MIRT_NODE_EMPTY whose sphere <
+   num_spheres; every other leaf is dead, contributes nothing and is counted in
+   dead_leaves).
+     area(i)   2 (dx dy + dy dz + dz dx) of node i's box in fp32, the builder's
+               own box area (bvh.c:48-57), operation for operation.
+     overhead  sum area(inner nodes) / sum area(hit-able leaves); +inf when the
+               leaf sum is 0 and the inner sum is not, 0 when both are.
+     cost      0.125 * overhead + 1, the builder's constants (bvh.c:96).
+   In a builder tree a hit-able leaf's box is its sphere's own box, so the leaf
+   sum is the same for a refit tree and for any rebuild of the same spheres:
+   cost / (cost when the tree was built) says how far the refit tree has
+   decayed. It is 1.000 under translation, uniform scaling and (to 0.5 %)
+   rotation, and tracked the cost ratio of refit to rebuilt tree within 6 % for
+   diffusing spheres on the host (10k spheres). The cost normalised by the
+   root's area does not: it FALLS when diffusing spheres grow the root.
+   The sums are exact and independent of the order of addition: with A0 =
+   area(0) and e = ilogb(A0) + 1, a term is trunc((double)area(i) * 2^(48 - e))
+   as a uint64; a term that is not >= 0 counts as 0, one above A0 as 2^48
+   (both counted in `clamped`: the boxes do not nest); the terms' halves
+   t >> 24 and t & 0xffffff are added apart in uint64 and a sum is
+   ldexp((double)hi * 2^24 + (double)lo, e - 48). The host and the device
+   (mirt_scene_quality) therefore return the same bytes. */
+typedef struct mirt_tree_quality {
+    double  inner_area, leaf_area;   /* the two sums, in the tree's own units */
+    double  overhead, cost;          /* inner_area / leaf_area; 0.125 * overhead + 1 */
+    float   root_area;
+    int32_t inner_nodes, leaves, dead_leaves;  /* leaves: hit-able ones */
+    int32_t clamped;                 /* terms outside [0, root_area] */
+    int32_t degenerate;              /* 1: root_area is not a positive finite float; sums, overhead, cost and
+                                        clamped are 0 */
+} mirt_tree_quality;
+/* The tree is checked as by mirt_bvh_validate_flat (MIRT_E_INVALID);
+   num_nodes == 0 is MIRT_OK with *out all zero. Never touches the GPU. */
+int mirt_bvh_quality_flat(const mirt_node *nodes, int num_nodes, int num_spheres, mirt_tree_quality *out);
+/* The same of the ctx's resident tree, whichever call installed it and whether
+   or not it admits ordered walks, by a kernel (csrc/quality_device.hip): one
+   thread per node, one read-back. A scene without a tree gives all zeros.
+   MIRT_E_NOSCENE without a scene; a NULL ctx or out is MIRT_E_INVALID before
+   any HIP call. Blocking. */
+int mirt_scene_quality(mirt_ctx *ctx, mirt_tree_quality *out);
+
+/* Refit the resident scene to `spheres` (the scene's order, as for
+   mirt_scene_refit_device), measure the refit tree, and rebuild instead when
+   it has decayed past max_decay:
+     base    the cost of the tree the ctx's last mirt_scene_update_device
+             installed. Every other install (upload, build, plain refit) leaves
+             the ctx without one; this call then measures the resident tree
+             first and takes its cost.
+     decay   cost of the refit tree / base; 1 when either is not a positive
+             finite number.
+     decay <= max_decay, or max_decay <= 0 (never rebuild): the refit tree is
+             installed, exactly what mirt_scene_refit_device installs. The base
+             stays, `reordered` is a copy of `spheres`, `perm` the identity.
+     else    the tree of spheres[start, end) is built from depth 0 and installed,
+             exactly what mirt_scene_build_device installs; its cost is the new
+             base. reordered[i] is spheres[perm[i]]: perm is what the colour
+             words hold after mirt_bvh_build_flat ran on a copy whose colour
+             words were replaced by the spheres' indices, so a caller can carry
+             its own per-sphere state through the rebuild.
+   reordered and perm (num_spheres each) and out may be NULL. Inputs that
+   mirt_scene_refit_device or the device build decline take the host path --
+   mirt_bvh_refit_flat, mirt_bvh_quality_flat, then mirt_scene_upload_flat of
+   the refit tree or of mirt_bvh_build_flat's -- with the same result and
+   on_device = 0. Arguments are checked as mirt_scene_refit_device checks them,
+   plus 0 <= start <= end. A failure leaves the old scene and the old base in
+   place (on the host path: a failure up to mirt_scene_upload_flat does);
+   frames already enqueued finish on the old scene. Blocking. What max_decay
+   to choose: decay follows the SAH cost, and frame time grows faster than
+   that -- measured on an MI355X at 1080p / 10k spheres, a refit scene at
+   decay 1.04 / 1.25 / 2.8 rendered 1.12 / 1.64 / 5.8 times as long as a
+   rebuild of the same spheres (MEASUREMENTS.md section E). */
+typedef struct mirt_update_result {
+    int32_t rebuilt;      /* 1: the scene was rebuilt; 0: refit */
+    int32_t on_device;    /* 0: a declined input took the host path */
+    double  base_cost, cost, decay;   /* cost is the refit tree's, measured before the decision */
+    mirt_tree_quality installed;      /* of the tree now resident */
+    float   total_ms;     /* call to return, host clock */
+} mirt_update_result;
+int mirt_scene_update_device(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres, int start, int end,
+                             double max_decay, mirt_sphere *reordered, int32_t *perm, mirt_update_result *out);
 
 /* ---------------------------------------------------------- rendering */
 
