@@ -37,48 +37,11 @@
 #include <vector>
 
 #include "internal.h"
+#include "tree.h"
 
 namespace {
 
-struct Box {
-    float lo[3], hi[3];
-};
-
-inline Box box_empty()  // bvh.c:19-24
-{
-    Box b;
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = INFINITY;
-        b.hi[a] = -INFINITY;
-    }
-    return b;
-}
-
-inline void box_add(Box& b, const mirt_sphere& s)  // bvh.c:26-46
-{
-    const float c[3] = {s.center.x, s.center.y, s.center.z};
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = std::fmin(b.lo[a], c[a] - s.radius);
-        b.hi[a] = std::fmax(b.hi[a], c[a] + s.radius);
-    }
-}
-
-inline void box_merge(Box& b, const Box& o)
-{
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = std::fmin(b.lo[a], o.lo[a]);
-        b.hi[a] = std::fmax(b.hi[a], o.hi[a]);
-    }
-}
-
-inline float box_area(const Box& b)  // bvh.c:48-57
-{
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    float s = dx * dy;
-    s = s + dy * dz;
-    s = s + dz * dx;
-    return 2.0f * s;
-}
+using namespace mirt;
 
 inline float centre(const mirt_sphere& s, int axis)
 {
@@ -139,14 +102,6 @@ struct FlatBuilder {
 
     uint32_t cur = 0;  // final-array index (relative to this builder) of the next node
 
-    void emit_box(mirt_node& n, const Box& b)
-    {
-        for (int a = 0; a < 3; a++) {
-            n.bmin[a] = b.lo[a];
-            n.bmax[a] = b.hi[a];
-        }
-    }
-
     void build(int lo, int hi, int depth)
     {
         const int me = (int)nodes.size();  // slot in `nodes`
@@ -155,7 +110,7 @@ struct FlatBuilder {
         counts.push_back(0);
         Box bounds = box_empty();
         for (int i = lo; i < hi; i++) box_add(bounds, s[i]);
-        emit_box(nodes[me], bounds);
+        store_box(nodes[me], bounds);
         const int n = hi - lo;
         if (n <= 1 || depth >= 40) {  // bvh.c:131-137 (n == 0 leaves too)
             nodes[me].sphere = lo;
@@ -169,7 +124,7 @@ struct FlatBuilder {
         for (int axis = 0; axis < 3; axis++) {
             float split[8];
             for (int i = 1; i < 8; i++)  // bvh.c:150/154/158
-                split[i] = bounds.lo[axis] + ((float)i / 8.0f) * (bounds.hi[axis] - bounds.lo[axis]);
+                split[i] = split_plane(bounds.lo[axis], bounds.hi[axis], i);
             Box bin_box[9];
             int bin_n[9] = {0};
             for (int k = 1; k <= 8; k++) bin_box[k] = box_empty();
@@ -200,10 +155,7 @@ struct FlatBuilder {
                 nr[i - 1] = cnt;
             }
             for (int i = 1; i < 8; i++) {
-                const float la = box_area(left[i]), ra = box_area(right[i]);
-                float sum = (float)nl[i] * la;  // bvh.c:96
-                sum = sum + (float)nr[i] * ra;
-                const float cost = 0.125f + sum;
+                const float cost = sah_cost(nl[i], box_area(left[i]), nr[i], box_area(right[i]));
                 if (cost < best_cost) {
                     best_cost = cost;
                     best_axis = axis;

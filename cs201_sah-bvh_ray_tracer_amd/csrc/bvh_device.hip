@@ -11,8 +11,9 @@
 //   classify   leaf (n <= 1 or depth >= 40) or inner; inner nodes take a pair
 //              of child slots in the next level. Their count is read back
 //              once: the node and bin arrays are sized from it, never guessed;
-//   bin, sah   bvh_build.cpp's 8 bins per axis and its cost expression,
-//              operation for operation (no contraction: -ffp-contract=off);
+//   bin, sah   bvh_build.cpp's 8 bins per axis; the planes, the areas and the
+//              cost are tree.h's split_plane, box_area and sah_cost, which the
+//              host builder calls too (no contraction: -ffp-contract=off);
 //              nodes of at most kSmall spheres are binned by their own SAH
 //              thread instead of by atomics, by the same rule;
 //   partition  the reference's swap loop (bvh.c:172-201) in closed form. With
@@ -44,17 +45,20 @@
 #include <new>
 #include <vector>
 
+#include "device_util.h"
 #include "internal.h"
+#include "tree.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBlock = 256;
+using namespace mirt;
+
+constexpr int kBlock = kScanBlock;
 constexpr int kItems = 8;
 constexpr int kChunk = kBlock * kItems;  // spheres per workgroup of the bounds / bin passes
-constexpr int kTile = 4 * kBlock;        // spheres per workgroup of the prefix sum
-constexpr int kSumBlock = 1024;          // the one workgroup that scans the tile sums
+constexpr int kTile = kScanTile;         // spheres per workgroup of the prefix sum
 constexpr int kBinWords = 168;           // per inner node: 3 x 8 counts, 3 x 8 x 3 lo keys, 3 x 8 x 3 hi keys
 constexpr int kBinLo = 24, kBinHi = 96;
 constexpr int kKeyPosInf = 0x7f800000;       // fkey(+inf)
@@ -92,40 +96,7 @@ __device__ __forceinline__ float funkey(int k) { return __int_as_float(k >= 0 ? 
 
 __device__ __forceinline__ float comp(const float4& g, int axis) { return axis == 0 ? g.x : (axis == 1 ? g.y : g.z); }
 
-// bvh.c:150/154/158
-__device__ __forceinline__ float split_plane(float lo, float hi, int i) { return lo + ((float)i / 8.0f) * (hi - lo); }
-
 __device__ __forceinline__ bool goes_left(const BNode& nd, const float4& g) { return comp(g, nd.axis) < nd.split; }
-
-// min / max into global memory. The plain read may be stale, which only means
-// an atomic that changes nothing: the values move one way.
-__device__ __forceinline__ void global_min(int* p, int v)
-{
-    if (v < *(volatile int*)p) atomicMin(p, v);
-}
-__device__ __forceinline__ void global_max(int* p, int v)
-{
-    if (v > *(volatile int*)p) atomicMax(p, v);
-}
-
-// exclusive prefix sum of one value per thread over a workgroup of B threads
-template <int B>
-__device__ int block_excl_scan(int v, int* sh, int* total)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < B; off <<= 1) {
-        const int x = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    const int incl = sh[t];
-    *total = sh[B - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 // ---- first and last pass: the caller's 20-byte spheres <-> (centre, radius) + colour
 
@@ -135,16 +106,8 @@ __global__ void prep_kernel(const uint32_t* aos, int n, float4* geo, uint32_t* c
     if (i >= n) return;
     const uint32_t* s = aos + 5 * (size_t)i;
     const uint32_t w[4] = {s[0], s[1], s[2], s[3]};
-    bool bad = false;
-    for (int k = 0; k < 4; k++) bad |= (w[k] & 0x7f800000u) == 0x7f800000u;  // NaN or infinite
-    const float4 g = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]),
-                                 __uint_as_float(w[3]));
-    for (int a = 0; a < 3; a++) {
-        const float c = comp(g, a);
-        bad |= __float_as_uint(c - g.w) == 0x80000000u || __float_as_uint(c + g.w) == 0x80000000u;
-    }
-    if (bad) atomicOr(&ctl[kCtlDeclined], 1);
-    geo[i] = g;
+    if (sphere_declined(w[0], w[1], w[2], w[3])) atomicOr(&ctl[kCtlDeclined], 1);
+    geo[i] = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
     col[i] = s[4];
     nof[i] = 0;
 }
@@ -247,7 +210,7 @@ __global__ void classify_kernel(BNode* nodes, int off, int cnt, int next_off, in
     if (valid && !inner) nd->left = -1;
 }
 
-// ---- binned SAH (bvh_build.cpp:169-213)
+// ---- binned SAH (bvh_build.cpp FlatBuilder::build)
 
 __global__ void init_bins_kernel(int* bins, size_t words)
 {
@@ -351,14 +314,10 @@ __device__ __forceinline__ void kbox_merge(KBox& b, const int* bin, int idx)
         b.hi[a] = max(b.hi[a], bin[kBinHi + idx * 3 + a]);
     }
 }
-__device__ __forceinline__ float kbox_area(const KBox& b)  // bvh.c:48-57
+__device__ __forceinline__ float kbox_area(const KBox& b)
 {
-    const float dx = funkey(b.hi[0]) - funkey(b.lo[0]), dy = funkey(b.hi[1]) - funkey(b.lo[1]),
-                dz = funkey(b.hi[2]) - funkey(b.lo[2]);
-    float s = dx * dy;
-    s = s + dy * dz;
-    s = s + dz * dx;
-    return 2.0f * s;
+    return box_area(funkey(b.hi[0]) - funkey(b.lo[0]), funkey(b.hi[1]) - funkey(b.lo[1]),
+                    funkey(b.hi[2]) - funkey(b.lo[2]));
 }
 
 __global__ void sah_kernel(const float4* geo, BNode* nodes, int off, int cnt, int next_off, const int* bins)
@@ -421,10 +380,7 @@ __global__ void sah_kernel(const float4* geo, BNode* nodes, int off, int cnt, in
         for (int i = 1; i < 8; i++) {  // left of plane i = bins 1..i
             kbox_merge(acc, bin, a * 8 + i - 1);
             c += bin[a * 8 + i - 1];
-            const float la = kbox_area(acc), ra = kbox_area(right[i]);
-            float sum = (float)c * la;  // bvh.c:96
-            sum = sum + (float)nr[i] * ra;
-            const float cost = 0.125f + sum;
+            const float cost = sah_cost(c, kbox_area(acc), nr[i], kbox_area(right[i]));
             if (cost < best_cost) {
                 best_cost = cost;
                 best_axis = a;
@@ -449,38 +405,8 @@ __device__ __forceinline__ bool left_flag(const float4* geo, const int* nof, con
 // rank[i] = left flags before i within its tile, tsum[tile] = flags of the tile; i runs to n inclusive
 __global__ void scan_tiles_kernel(const float4* geo, const int* nof, int n, const BNode* nodes, int* rank, int* tsum)
 {
-    __shared__ int sh[kBlock];
-    const int i0 = blockIdx.x * kTile + threadIdx.x * 4;
-    int f[4], s = 0;
-    for (int j = 0; j < 4; j++) {
-        f[j] = i0 + j < n && left_flag(geo, nof, nodes, i0 + j) ? 1 : 0;
-        s += f[j];
-    }
-    int total;
-    int run = block_excl_scan<kBlock>(s, sh, &total);
-    for (int j = 0; j < 4; j++) {
-        if (i0 + j <= n) rank[i0 + j] = run;
-        run += f[j];
-    }
-    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+    scan_tile([=](int i) { return left_flag(geo, nof, nodes, i) ? 1 : 0; }, n, n + 1, rank, &tsum[blockIdx.x]);
 }
-
-// exclusive prefix sum of the tile sums, in place, by one workgroup
-__global__ void scan_sums_kernel(int* tsum, int tiles)
-{
-    __shared__ int sh[kSumBlock];
-    int carry = 0;
-    for (int base = 0; base < tiles; base += kSumBlock) {
-        const int i = base + (int)threadIdx.x;
-        const int v = i < tiles ? tsum[i] : 0;
-        int total;
-        const int ex = block_excl_scan<kSumBlock>(v, sh, &total);
-        if (i < tiles) tsum[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__device__ __forceinline__ int gsum(const int* rank, const int* tsum, int i) { return rank[i] + tsum[i / kTile]; }
 
 // counts of every inner node of the level, and its two children's records
 __global__ void children_kernel(BNode* nodes, int off, int cnt, const int* rank, const int* tsum)
@@ -489,8 +415,8 @@ __global__ void children_kernel(BNode* nodes, int off, int cnt, const int* rank,
     if (j >= cnt) return;
     BNode& nd = nodes[off + j];
     if (nd.left < 0) return;
-    const int gb = gsum(rank, tsum, nd.lo);
-    const int nl = gsum(rank, tsum, nd.hi) - gb;
+    const int gb = scan_prefix(rank, tsum, nd.lo);
+    const int nl = scan_prefix(rank, tsum, nd.hi) - gb;
     nd.gbase = gb;
     nd.nl = nl;
     BNode ch{};
@@ -517,7 +443,7 @@ __global__ void jump_init_kernel(const float4* geo, const int* nof, int n, const
     if (k < 0) return;
     const BNode& nd = nodes[k];
     if (nd.left < 0) return;
-    if (goes_left(nd, geo[i])) jump[nd.lo + (gsum(rank, tsum, i) - nd.gbase)] = i;
+    if (goes_left(nd, geo[i])) jump[nd.lo + (scan_prefix(rank, tsum, i) - nd.gbase)] = i;
     if (i - nd.lo >= nd.nl) jump[i] = i;
 }
 
@@ -557,7 +483,7 @@ __global__ void scatter_kernel(const float4* geo, const uint32_t* col, const int
         const BNode& nd = nodes[k];
         if (nd.left >= 0) {
             const int mid = nd.lo + nd.nl;
-            if (goes_left(nd, g)) dst = nd.lo + (gsum(rank, tsum, i) - nd.gbase);
+            if (goes_left(nd, g)) dst = nd.lo + (scan_prefix(rank, tsum, i) - nd.gbase);
             else if (i < mid) dst = jump[i];
             child = dst < mid ? nd.left : nd.left + 1;
         }
@@ -607,18 +533,6 @@ struct Buf {
     size_t cap = 0;
 };
 
-int hip_fail(hipError_t e, const char* what)
-{
-    mirt::set_error("%s: %s", what, hipGetErrorString(e));
-    return MIRT_E_DEVICE;
-}
-
-#define HIP_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
 // at least `bytes`; keep: the first `keep` bytes survive a move
 int ensure(Buf& b, size_t bytes, hipStream_t s = nullptr, size_t keep = 0)
 {
@@ -639,8 +553,6 @@ int ensure(Buf& b, size_t bytes, hipStream_t s = nullptr, size_t keep = 0)
     b.cap = bytes;
     return MIRT_OK;
 }
-
-inline unsigned blocks(size_t items, int per) { return (unsigned)((items + (size_t)per - 1) / (size_t)per); }
 
 }  // namespace
 
@@ -721,7 +633,7 @@ int run_partition(BuildState& st, hipStream_t s, int cur, int n, int off, int cn
     int *rank = (int*)st.rank.p, *tsum = (int*)st.tsum.p, *jump = (int*)st.jump.p;
     const int tiles = (int)(((size_t)n + 1 + kTile - 1) / kTile);
     scan_tiles_kernel<<<tiles, kBlock, 0, s>>>(geo, nof, n, nodes, rank, tsum);
-    scan_sums_kernel<<<1, kSumBlock, 0, s>>>(tsum, tiles);
+    scan_sums_kernel<kSumBlock><<<1, kSumBlock, 0, s>>>(tsum, tiles, nullptr);
     children_kernel<<<blocks(cnt, kBlock), kBlock, 0, s>>>(nodes, off, cnt, rank, tsum);
     const unsigned g = blocks(n, kBlock);
     jump_init_kernel<<<g, kBlock, 0, s>>>(geo, nof, n, nodes, rank, tsum, jump);

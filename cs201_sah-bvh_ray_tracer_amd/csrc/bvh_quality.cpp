@@ -20,8 +20,7 @@ namespace mirt {
 void quality_finish(const QualitySums& q, mirt_tree_quality* out)
 {
     std::memset(out, 0, sizeof *out);
-    float a0;
-    std::memcpy(&a0, &q.root_area_bits, 4);
+    const float a0 = bits_float(q.root_area_bits);
     out->root_area = a0;
     out->inner_nodes = q.inner_nodes;
     out->leaves = q.leaves;
@@ -56,20 +55,20 @@ int mirt_bvh_quality_flat(const mirt_node* nodes, int num_nodes, int num_spheres
     std::memset(out, 0, sizeof *out);
     if (num_nodes == 0) return MIRT_OK;
     mirt::QualitySums q{};
-    const float a0 = mirt::quality_node_area(nodes[0]);
-    q.root_area_bits = mirt::quality_float_bits(a0);
+    const float a0 = mirt::box_area(nodes[0]);
+    q.root_area_bits = mirt::float_bits(a0);
     const bool ok = mirt::quality_root_ok(a0);
     const double scale = ok ? mirt::quality_scale(mirt::quality_exponent(a0)) : 0.0;
     for (int i = 0; i < num_nodes; i++) {
         const mirt_node& n = nodes[i];
         const bool inner = n.sphere < 0;
-        if (!inner && !mirt::quality_hitable(n, num_spheres)) {
+        if (mirt::dead_leaf(n, num_spheres)) {
             q.dead_leaves++;
             continue;
         }
         (inner ? q.inner_nodes : q.leaves)++;
         if (!ok) continue;
-        const uint64_t t = mirt::quality_term(mirt::quality_node_area(n), a0, scale, &q.clamped);
+        const uint64_t t = mirt::quality_term(mirt::box_area(n), a0, scale, &q.clamped);
         (inner ? q.inner_hi : q.leaf_hi) += t >> 24;
         (inner ? q.inner_lo : q.leaf_lo) += t & 0xffffffu;
     }

@@ -24,46 +24,9 @@
 #include <vector>
 
 #include "internal.h"
+#include "tree.h"
 
-namespace {
-
-struct Box {
-    float lo[3], hi[3];
-};
-
-inline Box box_empty()  // bvh.c:19-24
-{
-    Box b;
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = INFINITY;
-        b.hi[a] = -INFINITY;
-    }
-    return b;
-}
-
-inline void box_add(Box& b, const mirt_sphere& s)  // bvh.c:26-46
-{
-    const float c[3] = {s.center.x, s.center.y, s.center.z};
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = std::fmin(b.lo[a], c[a] - s.radius);
-        b.hi[a] = std::fmax(b.hi[a], c[a] + s.radius);
-    }
-}
-
-inline void box_merge(Box& b, const Box& o)
-{
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = std::fmin(b.lo[a], o.lo[a]);
-        b.hi[a] = std::fmax(b.hi[a], o.hi[a]);
-    }
-}
-
-inline bool hitable(const mirt_node& n, int ns)
-{
-    return n.sphere >= 0 && !(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns;
-}
-
-}  // namespace
+using namespace mirt;
 
 extern "C" {
 
@@ -102,7 +65,7 @@ try {
         const mirt_node& n = nodes[i];
         Box b = box_empty();
         if (n.sphere < 0) {
-            const uint32_t l = (uint32_t)i + 1, r = nodes[l].skip & MIRT_SKIP_MASK;
+            const uint32_t l = (uint32_t)i + 1, r = skip_of(nodes[l]);
             b = box[l];
             box_merge(b, box[r]);
         } else if (hitable(n, ns)) {
@@ -113,11 +76,8 @@ try {
     }
     for (int i = 0; i < nn; i++) {
         mirt_node& n = nodes[i];
-        if (n.sphere >= 0 && !hitable(n, ns)) continue;
-        for (int a = 0; a < 3; a++) {
-            n.bmin[a] = box[(size_t)i].lo[a];
-            n.bmax[a] = box[(size_t)i].hi[a];
-        }
+        if (dead_leaf(n, ns)) continue;
+        store_box(n, box[(size_t)i]);
     }
     return MIRT_OK;
 } catch (const std::bad_alloc&) {

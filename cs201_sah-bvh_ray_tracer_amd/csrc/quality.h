@@ -2,7 +2,7 @@
 // bvh_quality.cpp (host) and quality_device.hip (kernel) share, so that both
 // paths form every term and every sum from the same operations.
 //
-//   area      box_area of bvh_build.cpp (bvh.c:48-57), fp32, uncontracted;
+//   area      box_area of tree.h (bvh.c:48-57), fp32, uncontracted;
 //   e         ilogb(A0) + 1 of the root's area A0: every area in [0, A0] is
 //             below 2^e;
 //   term      trunc((double)area * 2^(48 - e)) as a uint64, below 2^48 (the
@@ -19,12 +19,7 @@
 #include <cstring>
 
 #include "../../include/mirt.h"
-
-#if defined(__HIPCC__)
-#define MIRT_HD __host__ __device__
-#else
-#define MIRT_HD
-#endif
+#include "tree.h"
 
 namespace mirt {
 
@@ -34,32 +29,16 @@ struct QualitySums {
     uint32_t root_area_bits, pad;
 };
 
-MIRT_HD inline uint32_t quality_float_bits(float f)
-{
-    uint32_t b;
-    memcpy(&b, &f, 4);
-    return b;
-}
-
-MIRT_HD inline float quality_node_area(const mirt_node& n)  // bvh_build.cpp box_area
-{
-    const float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-    float s = dx * dy;
-    s = s + dy * dz;
-    s = s + dz * dx;
-    return 2.0f * s;
-}
-
 // a positive finite float (else the tree is degenerate)
 MIRT_HD inline bool quality_root_ok(float a0)
 {
-    return a0 > 0.0f && (quality_float_bits(a0) & 0x7f800000u) != 0x7f800000u;
+    return a0 > 0.0f && (float_bits(a0) & 0x7f800000u) != 0x7f800000u;
 }
 
 // ilogb(a0) + 1 of a positive finite float: in [-148, 128]
 MIRT_HD inline int quality_exponent(float a0)
 {
-    const uint32_t b = quality_float_bits(a0);
+    const uint32_t b = float_bits(a0);
     const int ex = (int)((b >> 23) & 0xffu);
     if (ex) return ex - 126;
     uint32_t m = b & 0x7fffffu;  // subnormal: m * 2^-149, m > 0
@@ -91,11 +70,6 @@ MIRT_HD inline uint64_t quality_term(float area, float a0, double scale, int32_t
         return (uint64_t)1 << 48;
     }
     return (uint64_t)((double)area * scale);
-}
-
-MIRT_HD inline bool quality_hitable(const mirt_node& n, int ns)
-{
-    return n.sphere >= 0 && !(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns;
 }
 
 inline double quality_sum_value(uint64_t hi, uint64_t lo, int e)

@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "device_util.h"
 #include "internal.h"
 #include "quality.h"
 
@@ -52,16 +53,16 @@ __global__ void quality_kernel(const mirt_node* nd, int nn, int ns, Slot* ctl)
 {
     __shared__ unsigned long long sh[kWaves][kWords];
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    const float a0 = quality_node_area(nd[0]);
+    const float a0 = box_area(nd[0]);
     const bool ok = quality_root_ok(a0);
     const double scale = ok ? quality_scale(quality_exponent(a0)) : 0.0;
     // inner hi / lo, leaf hi / lo, inner nodes, leaves, dead leaves, clamped
     unsigned long long v[kWords] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (i < nn) {
         const mirt_node n = nd[i];
-        const bool inner = n.sphere < 0, dead = !inner && !quality_hitable(n, ns);
+        const bool inner = n.sphere < 0, dead = dead_leaf(n, ns);
         int32_t clamped = 0;
-        const uint64_t t = ok && !dead ? quality_term(quality_node_area(n), a0, scale, &clamped) : 0;
+        const uint64_t t = ok && !dead ? quality_term(box_area(n), a0, scale, &clamped) : 0;
         const unsigned long long hi = t >> 24, lo = t & 0xffffffu;
         v[0] = inner ? hi : 0;
         v[1] = inner ? lo : 0;
@@ -91,28 +92,8 @@ __global__ void quality_kernel(const mirt_node* nd, int nn, int ns, Slot* ctl)
     int* counts = &ctl->q.inner_nodes;  // inner_nodes, leaves, dead_leaves, clamped
     for (int k = 0; k < 4; k++)
         if (t[4 + k]) atomicAdd(&counts[k], (int)t[4 + k]);
-    if (blockIdx.x == 0) ctl->q.root_area_bits = quality_float_bits(a0);
+    if (blockIdx.x == 0) ctl->q.root_area_bits = float_bits(a0);
 }
-
-int hip_fail(hipError_t e, const char* what)
-{
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return MIRT_E_DEVICE;
-}
-
-#define HIP_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 
 }  // namespace
 
@@ -124,8 +105,7 @@ int mirt::quality_device(hipStream_t s, const mirt_node* d_nodes, int nn, int ns
     DevMem ctl;
     HIP_TRY(hipMalloc(&ctl.p, sizeof(Slot) * kSlots));
     HIP_TRY(hipMemsetAsync(ctl.p, 0, sizeof(Slot) * kSlots, s));
-    const unsigned grid = (unsigned)(((size_t)nn + kBlock - 1) / kBlock);
-    quality_kernel<<<grid, kBlock, 0, s>>>(d_nodes, nn, ns, (Slot*)ctl.p);
+    quality_kernel<<<blocks((size_t)nn, kBlock), kBlock, 0, s>>>(d_nodes, nn, ns, (Slot*)ctl.p);
     HIP_TRY(hipGetLastError());
     Slot slots[kSlots];
     HIP_TRY(hipMemcpyAsync(slots, ctl.p, sizeof(Slot) * kSlots, hipMemcpyDeviceToHost, s));

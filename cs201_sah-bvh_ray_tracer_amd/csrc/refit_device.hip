@@ -19,7 +19,8 @@
 // spheres increase in pre-order, every mark is set once, and no node is deeper
 // than 62: ndepth is exact. A box is fmin / fmax over finite values none of
 // which is -0.0 (declined), so the order of combination does not show: the
-// host's bits. Every loop is bounded at launch; no workgroup waits on another.
+// host's bits, from the box operations of tree.h that bvh_refit.cpp folds with.
+// Every loop is bounded at launch; no workgroup waits on another.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,8 +31,10 @@
 #include <new>
 #include <vector>
 
+#include "device_util.h"
 #include "internal.h"
 #include "quality.h"
+#include "tree.h"
 
 #pragma clang fp contract(off)
 
@@ -52,52 +55,16 @@ enum {
     kCtlWords = 8
 };
 
-struct Box {
-    float lo[3], hi[3];
-};
-
-__device__ __forceinline__ Box box_empty()
-{
-    Box b;
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = __uint_as_float(0x7f800000u);
-        b.hi[a] = __uint_as_float(0xff800000u);
-    }
-    return b;
-}
-
-__device__ __forceinline__ void box_add(Box& b, const uint32_t* aos, int k)
+__device__ __forceinline__ void add_sphere(Box& b, const uint32_t* aos, int k)
 {
     const uint32_t* s = aos + 5 * (size_t)k;
-    const float r = __uint_as_float(s[3]);
-    for (int a = 0; a < 3; a++) {
-        const float c = __uint_as_float(s[a]);
-        b.lo[a] = fminf(b.lo[a], c - r);
-        b.hi[a] = fmaxf(b.hi[a], c + r);
-    }
-}
-
-__device__ __forceinline__ bool hitable(const mirt_node& n, int ns)
-{
-    return n.sphere >= 0 && !(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns;
+    box_add(b, __uint_as_float(s[0]), __uint_as_float(s[1]), __uint_as_float(s[2]), __uint_as_float(s[3]));
 }
 
 // a child's box into its parent's; a dead leaf contributes the empty box
-__device__ __forceinline__ void box_merge(Box& b, const mirt_node& child, int ns)
+__device__ __forceinline__ void merge_child(Box& b, const mirt_node& child, int ns)
 {
-    if (child.sphere >= 0 && !hitable(child, ns)) return;
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = fminf(b.lo[a], child.bmin[a]);
-        b.hi[a] = fmaxf(b.hi[a], child.bmax[a]);
-    }
-}
-
-__device__ __forceinline__ void store_box(mirt_node* out, int i, const Box& b)
-{
-    for (int a = 0; a < 3; a++) {
-        out[i].bmin[a] = b.lo[a];
-        out[i].bmax[a] = b.hi[a];
-    }
+    if (!dead_leaf(child, ns)) box_merge(b, node_box(child));
 }
 
 // mark: ns + 1 bytes, zeroed
@@ -110,11 +77,11 @@ __global__ void mark_kernel(const mirt_node* nd, int nn, int ns, const uint8_t* 
     out[i] = n;
     if (n.sphere < 0) {
         const int d = ndepth[i];
-        if (d > *(volatile int*)&ctl[kMaxDepth]) atomicMax(&ctl[kMaxDepth], d);
+        global_max(&ctl[kMaxDepth], d);
     } else if (hitable(n, ns)) {
         mark[n.sphere] = 1;
-        if (n.sphere < *(volatile int*)&ctl[kMinLive]) atomicMin(&ctl[kMinLive], n.sphere);
-        if (n.sphere > *(volatile int*)&ctl[kMaxLive]) atomicMax(&ctl[kMaxLive], n.sphere);
+        global_min(&ctl[kMinLive], n.sphere);
+        global_max(&ctl[kMaxLive], n.sphere);
     }
 }
 
@@ -123,14 +90,7 @@ __global__ void decline_kernel(const uint32_t* aos, int end, int* ctl)
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= end || i < ctl[kMinLive]) return;
     const uint32_t* s = aos + 5 * (size_t)i;
-    bool bad = false;
-    for (int k = 0; k < 4; k++) bad |= (s[k] & 0x7f800000u) == 0x7f800000u;
-    const float r = __uint_as_float(s[3]);
-    for (int a = 0; a < 3; a++) {
-        const float c = __uint_as_float(s[a]);
-        bad |= __float_as_uint(c - r) == 0x80000000u || __float_as_uint(c + r) == 0x80000000u;
-    }
-    if (bad && !*(volatile int*)&ctl[kDeclined]) atomicOr(&ctl[kDeclined], 1);
+    if (sphere_declined(s[0], s[1], s[2], s[3])) flag(ctl, kDeclined);
 }
 
 // queue: nn ints
@@ -143,13 +103,13 @@ __global__ void leaves_kernel(const mirt_node* nd, int nn, int ns, const uint32_
     if (!hitable(n, ns) || n.sphere >= end) return;  // end <= a leaf's sphere: the host refuses the call
     Box b = box_empty();
     int k = n.sphere;
-    for (int step = 0; step < kShort && k < end && (k == n.sphere || !mark[k]); step++, k++) box_add(b, aos, k);
+    for (int step = 0; step < kShort && k < end && (k == n.sphere || !mark[k]); step++, k++) add_sphere(b, aos, k);
     if (k < end && !mark[k]) {
         const int q = atomicAdd(&ctl[kLong], 1);
         if (q < nn) queue[q] = i;
         return;
     }
-    store_box(out, i, b);
+    store_box(out[i], b);
 }
 
 // one wave per queued leaf
@@ -167,7 +127,7 @@ __global__ void long_leaves_kernel(const mirt_node* nd, int nn, const uint32_t* 
         const bool in = k < end && (k == first || !mark[k]);
         const unsigned long long stop = __ballot(!in);
         const bool mine = stop ? lane < __builtin_ctzll(stop) : true;
-        if (mine) box_add(b, aos, k);
+        if (mine) add_sphere(b, aos, k);
         if (stop) break;
     }
     for (int off = 32; off > 0; off >>= 1)
@@ -175,7 +135,7 @@ __global__ void long_leaves_kernel(const mirt_node* nd, int nn, const uint32_t* 
             b.lo[a] = fminf(b.lo[a], __shfl_xor(b.lo[a], off));
             b.hi[a] = fmaxf(b.hi[a], __shfl_xor(b.hi[a], off));
         }
-    if (lane == 0) store_box(out, i, b);
+    if (lane == 0) store_box(out[i], b);
 }
 
 // the inner nodes of depth d from their children, which the launches before finished
@@ -184,13 +144,13 @@ __global__ void level_kernel(mirt_node* out, int nn, int ns, const uint8_t* ndep
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nn || ndepth[i] != d || out[i].sphere >= 0 || i + 1 >= nn) return;
     const mirt_node l = out[i + 1];
-    const uint32_t ri = l.skip & MIRT_SKIP_MASK;
+    const uint32_t ri = skip_of(l);
     if (ri >= (uint32_t)nn) return;
     const mirt_node r = out[ri];
     Box b = box_empty();
-    box_merge(b, l, ns);
-    box_merge(b, r, ns);
-    store_box(out, i, b);
+    merge_child(b, l, ns);
+    merge_child(b, r, ns);
+    store_box(out[i], b);
 }
 
 // mirt_scene_update_device's rebuild: the build ran on spheres whose colour word held their index, and the
@@ -205,28 +165,6 @@ __global__ void perm_kernel(uint32_t* aos, int ns, const uint32_t* colour, int32
 }
 
 // ---- host side
-
-int hip_fail(hipError_t e, const char* what)
-{
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return MIRT_E_DEVICE;
-}
-
-#define HIP_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
-inline unsigned blocks(size_t items, int per) { return (unsigned)((items + (size_t)per - 1) / (size_t)per); }
-
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 
 // The refit kernels on stream s: d_tree[nn] from the resident tree and the spheres at d_aos. *verdict = 0: d_tree is
 // the refit tree once the stream has run; 1: an input the kernels decline. Blocking (one read-back).
@@ -272,27 +210,81 @@ int refit_kernels(hipStream_t s, const ResidentScene& rs, const uint32_t* d_aos,
     return MIRT_OK;
 }
 
-// exactly one of `spheres` (host) and `d_spheres` (device) is set, unless ns == 0
-int refit(mirt_ctx* c, const mirt_sphere* spheres, const void* d_spheres, int ns, int end, mirt_node* out_nodes,
-          const char* fn)
-try {
+// The checked entry of both calls: the ctx, the counts (`args_ok`: the caller's own test of them) and the
+// resident scene, which must hold `ns` spheres.
+int resident_scene(mirt_ctx* c, bool args_ok, int ns, ResidentScene* rs, const char* fn)
+{
     if (!c) {
         set_error("%s: null context", fn);
         return MIRT_E_INVALID;
     }
-    if (ns < 0 || (ns > 0 && !spheres && !d_spheres) || end < 0 || end > ns) {
+    if (!args_ok) {
         set_error("%s: invalid arguments", fn);
         return MIRT_E_INVALID;
     }
-    ResidentScene rs{};
-    if (!ctx_resident_scene(c, &rs)) {
+    if (!ctx_resident_scene(c, rs)) {
         set_error("%s: no scene uploaded", fn);
         return MIRT_E_NOSCENE;
     }
-    if (ns != rs.num_spheres) {
-        set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs.num_spheres);
+    if (ns != rs->num_spheres) {
+        set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs->num_spheres);
         return MIRT_E_INVALID;
     }
+    return MIRT_OK;
+}
+
+// The refit stage of both calls: the moved spheres on the device at d_aos (the caller's d_spheres, else `spheres`
+// uploaded into `aos`) and the resident tree refit to them in `tree`. declined: the resident scene is not ordered or
+// the kernels decline an input; there is no refit tree and the host refits. Nothing is installed.
+struct Refit {
+    DevMem aos, tree;
+    const uint32_t* d_aos = nullptr;
+    int declined = 0;
+};
+int refit_stage(hipStream_t s, const ResidentScene& rs, const mirt_sphere* spheres, const void* d_spheres, int end,
+                Refit& r, const char* fn)
+{
+    const int nn = rs.num_nodes, ns = rs.num_spheres;
+    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns, tree_bytes = sizeof(mirt_node) * (size_t)nn;
+    r.declined = nn > 0 && !rs.ordered;
+    if (r.declined) return MIRT_OK;
+    r.d_aos = (const uint32_t*)d_spheres;
+    if (!r.d_aos) {
+        HIP_TRY(hipMalloc(&r.aos.p, std::max<size_t>(sph_bytes, 4)));
+        if (ns > 0) HIP_TRY(hipMemcpyAsync(r.aos.p, spheres, sph_bytes, hipMemcpyHostToDevice, s));
+        r.d_aos = (const uint32_t*)r.aos.p;
+    }
+    HIP_TRY(hipMalloc(&r.tree.p, std::max<size_t>(tree_bytes, sizeof(mirt_node))));
+    int rc = MIRT_OK;
+    if (nn > 0) rc = refit_kernels(s, rs, r.d_aos, end, (mirt_node*)r.tree.p, &r.declined, fn);
+    if (rc || r.declined) (void)hipStreamSynchronize(s);  // the arrays are freed on the caller's way out
+    return rc;
+}
+
+// The declined path's refit, on the host: the resident tree into `nodes`, refit there by mirt_bvh_refit_flat.
+// *spheres null: the caller's spheres are on the device, and are fetched into `copy` first.
+int host_refit(hipStream_t s, const ResidentScene& rs, const mirt_sphere** spheres, const void* d_spheres, int end,
+               std::vector<mirt_sphere>& copy, std::vector<mirt_node>& nodes)
+{
+    const int nn = rs.num_nodes, ns = rs.num_spheres;
+    nodes.resize((size_t)nn);
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!*spheres && ns > 0) {
+        copy.resize((size_t)ns);
+        HIP_TRY(hipMemcpy(copy.data(), d_spheres, sizeof(mirt_sphere) * (size_t)ns, hipMemcpyDeviceToHost));
+        *spheres = copy.data();
+    }
+    if (nn > 0) HIP_TRY(hipMemcpy(nodes.data(), rs.nodes32, sizeof(mirt_node) * (size_t)nn, hipMemcpyDeviceToHost));
+    return mirt_bvh_refit_flat(nodes.data(), nn, *spheres, ns, end);
+}
+
+// exactly one of `spheres` (host) and `d_spheres` (device) is set, unless ns == 0
+int refit(mirt_ctx* c, const mirt_sphere* spheres, const void* d_spheres, int ns, int end, mirt_node* out_nodes,
+          const char* fn)
+try {
+    ResidentScene rs{};
+    if (int rc = resident_scene(c, ns >= 0 && (ns == 0 || spheres || d_spheres) && end >= 0 && end <= ns, ns, &rs, fn))
+        return rc;
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point t) {
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -300,29 +292,22 @@ try {
     HIP_TRY(hipSetDevice(ctx_device(c)));
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
     const int nn = rs.num_nodes;
-    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns, tree_bytes = sizeof(mirt_node) * (size_t)nn;
+    const size_t tree_bytes = sizeof(mirt_node) * (size_t)nn;
     mirt_refit_stats st{};
     st.nodes = nn;
-    int declined = nn > 0 && !rs.ordered;
-    if (!declined) {
-        DevMem aos, tree;
-        const uint32_t* d_aos = (const uint32_t*)d_spheres;
-        if (!d_aos) {
-            HIP_TRY(hipMalloc(&aos.p, std::max<size_t>(sph_bytes, 4)));
-            if (ns > 0) HIP_TRY(hipMemcpyAsync(aos.p, spheres, sph_bytes, hipMemcpyHostToDevice, s));
-            d_aos = (const uint32_t*)aos.p;
-        }
-        HIP_TRY(hipMalloc(&tree.p, std::max<size_t>(tree_bytes, sizeof(mirt_node))));
-        int rc = MIRT_OK;
-        if (nn > 0) rc = refit_kernels(s, rs, d_aos, end, (mirt_node*)tree.p, &declined, fn);
-        if (rc || declined) (void)hipStreamSynchronize(s);  // the arrays are freed on the way out
+    int declined;
+    {
+        Refit r;
+        int rc = refit_stage(s, rs, spheres, d_spheres, end, r, fn);
         if (rc) return rc;
+        declined = r.declined;
         if (!declined) {
             st.refit_ms = since(t0);
             const auto t1 = std::chrono::steady_clock::now();
-            rc = layout_device(c, s, d_aos, ns, (const mirt_node*)tree.p, nn, fn);
+            rc = layout_device(c, s, r.d_aos, ns, (const mirt_node*)r.tree.p, nn, fn);
             hipError_t e = hipSuccess;
-            if (!rc && out_nodes && nn > 0) e = hipMemcpyAsync(out_nodes, tree.p, tree_bytes, hipMemcpyDeviceToHost, s);
+            if (!rc && out_nodes && nn > 0)
+                e = hipMemcpyAsync(out_nodes, r.tree.p, tree_bytes, hipMemcpyDeviceToHost, s);
             const hipError_t e2 = hipStreamSynchronize(s);
             if (rc) return rc;
             if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, fn);
@@ -333,15 +318,8 @@ try {
     if (declined) {
         // the host refit and the host upload on the resident tree: the same result
         std::vector<mirt_sphere> copy;
-        std::vector<mirt_node> nodes((size_t)nn);
-        HIP_TRY(hipStreamSynchronize(s));
-        if (!spheres && ns > 0) {
-            copy.resize((size_t)ns);
-            HIP_TRY(hipMemcpy(copy.data(), d_spheres, sph_bytes, hipMemcpyDeviceToHost));
-            spheres = copy.data();
-        }
-        HIP_TRY(hipMemcpy(nodes.data(), rs.nodes32, tree_bytes, hipMemcpyDeviceToHost));
-        if (int rc = mirt_bvh_refit_flat(nodes.data(), nn, spheres, ns, end)) return rc;
+        std::vector<mirt_node> nodes;
+        if (int rc = host_refit(s, rs, &spheres, d_spheres, end, copy, nodes)) return rc;
         if (int rc = mirt_scene_upload_flat(c, spheres, ns, nodes.data(), nn)) return rc;
         if (out_nodes) std::memcpy(out_nodes, nodes.data(), tree_bytes);
     }
@@ -374,28 +352,14 @@ int update(mirt_ctx* c, const mirt_sphere* spheres, int ns, int start, int end, 
            mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
 try {
     const char* fn = "mirt_scene_update_device";
-    if (!c) {
-        set_error("%s: null context", fn);
-        return MIRT_E_INVALID;
-    }
-    if (ns < 0 || (ns > 0 && !spheres) || start < 0 || end < start || end > ns) {
-        set_error("%s: invalid arguments", fn);
-        return MIRT_E_INVALID;
-    }
     ResidentScene rs{};
-    if (!ctx_resident_scene(c, &rs)) {
-        set_error("%s: no scene uploaded", fn);
-        return MIRT_E_NOSCENE;
-    }
-    if (ns != rs.num_spheres) {
-        set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs.num_spheres);
-        return MIRT_E_INVALID;
-    }
+    const bool args_ok = ns >= 0 && (ns == 0 || spheres) && start >= 0 && end >= start && end <= ns;
+    if (int rc = resident_scene(c, args_ok, ns, &rs, fn)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx_device(c)));
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
     const int nn = rs.num_nodes;
-    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns, tree_bytes = sizeof(mirt_node) * (size_t)nn;
+    const size_t sph_bytes = sizeof(mirt_sphere) * (size_t)ns;
     mirt_update_result res;
     std::memset(&res, 0, sizeof res);
     double base = 0.0;
@@ -411,21 +375,17 @@ try {
         res.decay = quality_decay(q.cost, base);
         return max_decay > 0.0 && res.decay > max_decay;
     };
-    int declined = nn > 0 && !rs.ordered;
-    if (!declined) {
-        DevMem aos, tree;
-        HIP_TRY(hipMalloc(&aos.p, std::max<size_t>(sph_bytes, 4)));
-        if (ns > 0) HIP_TRY(hipMemcpyAsync(aos.p, spheres, sph_bytes, hipMemcpyHostToDevice, s));
-        const uint32_t* d_aos = (const uint32_t*)aos.p;
-        HIP_TRY(hipMalloc(&tree.p, std::max<size_t>(tree_bytes, sizeof(mirt_node))));
-        int rc = MIRT_OK;
-        if (nn > 0) rc = refit_kernels(s, rs, d_aos, end, (mirt_node*)tree.p, &declined, fn);
-        if (rc || declined) (void)hipStreamSynchronize(s);  // the arrays are freed on the way out
+    int declined;
+    {
+        Refit r;
+        int rc = refit_stage(s, rs, spheres, nullptr, end, r, fn);
         if (rc) return rc;
+        declined = r.declined;
+        const mirt_node* tree = (const mirt_node*)r.tree.p;
         mirt_tree_quality q;
-        if (!declined && (rc = quality_device(s, (const mirt_node*)tree.p, nn, ns, &q, fn))) return rc;
+        if (!declined && (rc = quality_device(s, tree, nn, ns, &q, fn))) return rc;
         if (!declined && !wants_rebuild(q)) {
-            rc = layout_device(c, s, d_aos, ns, (const mirt_node*)tree.p, nn, fn);
+            rc = layout_device(c, s, r.d_aos, ns, tree, nn, fn);
             const hipError_t e = hipStreamSynchronize(s);
             if (rc) return rc;
             if (e != hipSuccess) return hip_fail(e, fn);
@@ -473,10 +433,9 @@ try {
     }
     if (declined) {
         // the host refit, the host measure, then the host upload or the host build and upload: the same result
-        std::vector<mirt_node> nodes((size_t)nn);
-        HIP_TRY(hipStreamSynchronize(s));
-        if (nn > 0) HIP_TRY(hipMemcpy(nodes.data(), rs.nodes32, tree_bytes, hipMemcpyDeviceToHost));
-        if (int rc = mirt_bvh_refit_flat(nodes.data(), nn, spheres, ns, end)) return rc;
+        std::vector<mirt_sphere> unused;
+        std::vector<mirt_node> nodes;
+        if (int rc = host_refit(s, rs, &spheres, nullptr, end, unused, nodes)) return rc;
         mirt_tree_quality q;
         if (int rc = mirt_bvh_quality_flat(nodes.data(), nn, ns, &q)) return rc;
         if (!wants_rebuild(q)) {

@@ -11,7 +11,8 @@
 //             non-finite sphere, a box that does not nest, an orphaned
 //             phantom) are max / or reductions: exact in any order. The bound
 //             itself, cb (1 + 2^-10) + 2^-10 in double, is formed on the host
-//             from the reduced maxima, as scene_layout.cpp forms it;
+//             from the reduced maxima by layout_rules.h's layout_bound, which
+//             scene_layout.cpp calls too;
 //   PNodes    pidx = 1 + the rank of an inner node among the inner nodes in
 //             pre-order: an exclusive prefix sum of the inner flags;
 //   depth     of node i = inner nodes before i - inner subtrees that end at or
@@ -27,8 +28,9 @@
 //             and the level's two totals are read back once: the next launch
 //             is sized from them, never guessed.
 // Every kernel loop is bounded at launch; no workgroup waits on another. The
-// arithmetic (outward nextafter, fp16 rounding, the split's box area) is
-// scene_layout.cpp's, operation for operation, with no contraction.
+// arithmetic and the per-node decisions (outward rounding, the HNode cut, a
+// PNode child, a slot's packed box) are layout_rules.h's, the functions
+// scene_layout.cpp calls: only the numbering is stated twice.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,8 +42,10 @@
 #include <new>
 #include <vector>
 
+#include "device_util.h"
 #include "internal.h"
 #include "layout.h"
+#include "layout_rules.h"
 
 #pragma clang fp contract(off)
 
@@ -49,9 +53,8 @@ namespace {
 
 using namespace mirt;
 
-constexpr int kBlock = 256;
-constexpr int kTile = 4 * kBlock;  // elements per workgroup of the prefix sums
-constexpr int kSumBlock = 1024;    // the one workgroup that scans an array's tile sums
+constexpr int kBlock = kScanBlock;
+constexpr int kTile = kScanTile;  // elements per workgroup of the prefix sums
 
 // ctl words (device, read back by the host)
 enum {
@@ -72,136 +75,15 @@ enum {
     kCtlWords = 16
 };
 
-__device__ __forceinline__ void flag(int* ctl, int w)
-{
-    if (!*(volatile int*)&ctl[w]) atomicOr(&ctl[w], 1);
-}
-__device__ __forceinline__ void global_max(int* p, int v)
-{
-    if (v > *(volatile int*)p) atomicMax(p, v);
-}
 __device__ __forceinline__ bool finite_bits(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
-
-// nextafter(x, -inf) / nextafter(x, +inf)
-__device__ __forceinline__ float next_down(float x)
-{
-    const uint32_t b = __float_as_uint(x);
-    if (x != x || b == 0xff800000u) return x;
-    if ((b & 0x7fffffffu) == 0u) return __uint_as_float(0x80000001u);
-    return __uint_as_float((b & 0x80000000u) ? b + 1u : b - 1u);
-}
-__device__ __forceinline__ float next_up(float x)
-{
-    const uint32_t b = __float_as_uint(x);
-    if (x != x || b == 0x7f800000u) return x;
-    if ((b & 0x7fffffffu) == 0u) return __uint_as_float(0x00000001u);
-    return __uint_as_float((b & 0x80000000u) ? b - 1u : b + 1u);
-}
-
-// scene_layout.cpp's half_down / half_up: the nearest half, then stepped to the right side
-__device__ __forceinline__ uint32_t half_bits(float v)
-{
-    const _Float16 h = (_Float16)v;
-    return (uint32_t)__builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ float half_value(uint32_t b)
-{
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
-}
-__device__ __forceinline__ uint32_t half_down(float v)
-{
-    uint32_t b = half_bits(v);
-    for (int k = 0; k < 4 && half_value(b) > v; k++) b = b == 0x0000u ? 0x8001u : ((b & 0x8000u) ? b + 1u : b - 1u);
-    return b & 0xffffu;
-}
-__device__ __forceinline__ uint32_t half_up(float v)
-{
-    uint32_t b = half_bits(v);
-    for (int k = 0; k < 4 && half_value(b) < v; k++) b = b == 0x8000u ? 0x0001u : ((b & 0x8000u) ? b - 1u : b + 1u);
-    return b & 0xffffu;
-}
-
-__device__ __forceinline__ uint32_t skip_of(const mirt_node& n) { return n.skip & MIRT_SKIP_MASK; }
-
-__device__ __forceinline__ bool dead_leaf(const mirt_node* nd, uint32_t i, int ns)
-{
-    const mirt_node n = nd[i];
-    return n.sphere >= 0 && ((n.skip & MIRT_NODE_EMPTY) || n.sphere >= ns);
-}
-
-// scene_layout.cpp's live_node. Every step moves to a later node, so nn steps bound it.
-__device__ uint32_t live_node(const mirt_node* nd, int nn, int ns, uint32_t ci)
-{
-    for (int step = 0; step < nn && ci < (uint32_t)nn; step++) {
-        if (nd[ci].sphere >= 0) return dead_leaf(nd, ci, ns) ? kPNone : ci;
-        const uint32_t l = ci + 1;
-        if (l >= (uint32_t)nn) break;
-        const uint32_t r = skip_of(nd[l]);
-        if (r >= (uint32_t)nn) break;
-        const bool dl = dead_leaf(nd, l, ns), dr = dead_leaf(nd, r, ns);
-        if (dl && dr) return kPNone;
-        if (!dl && !dr) return ci;
-        ci = dl ? r : l;
-    }
-    return kPNone;  // not reached for a validated tree
-}
 
 // ---- prefix sums: `arrays` arrays of n ints, `stride` apart, each made exclusive within its tiles
 
-__device__ int block_excl_scan(int v, int* sh, int width, int* total)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < width; off <<= 1) {
-        const int x = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    const int incl = sh[t];
-    *total = sh[width - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 __global__ void scan_tiles_kernel(int* data, size_t stride, int n, int* tsum, int tiles)
 {
-    __shared__ int sh[kBlock];
     int* d = data + stride * blockIdx.y;
-    const int i0 = blockIdx.x * kTile + threadIdx.x * 4;
-    int f[4], s = 0;
-    for (int j = 0; j < 4; j++) {
-        f[j] = i0 + j < n ? d[i0 + j] : 0;
-        s += f[j];
-    }
-    int total;
-    int run = block_excl_scan(s, sh, kBlock, &total);
-    for (int j = 0; j < 4; j++) {
-        if (i0 + j < n) d[i0 + j] = run;
-        run += f[j];
-    }
-    if (threadIdx.x == 0) tsum[(size_t)tiles * blockIdx.y + blockIdx.x] = total;
+    scan_tile([=](int i) { return d[i]; }, n, n, d, &tsum[(size_t)tiles * blockIdx.y + blockIdx.x]);
 }
-
-// one workgroup per array: its tile sums made exclusive in place, the grand total to totals[array]
-__global__ void scan_sums_kernel(int* tsum, int tiles, int* totals)
-{
-    __shared__ int sh[kSumBlock];
-    int* ts = tsum + (size_t)tiles * blockIdx.x;
-    int carry = 0;
-    for (int base = 0; base < tiles; base += kSumBlock) {
-        const int i = base + (int)threadIdx.x;
-        const int v = i < tiles ? ts[i] : 0;
-        int total;
-        const int ex = block_excl_scan(v, sh, kSumBlock, &total);
-        if (i < tiles) ts[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-
-__device__ __forceinline__ int prefix(const int* data, const int* tsum, int i) { return data[i] + tsum[i / kTile]; }
 
 // ---- spheres: geo / color with their sentinels, r_max, c_max, the finite check
 
@@ -232,14 +114,6 @@ __global__ void spheres_kernel(const uint32_t* aos, int ns, float4* geo, uint32_
 
 // ---- nodes: DNodes, the nesting check, the three flag arrays, the coordinate bound
 
-__device__ __forceinline__ bool holds(const mirt_node& outer, const mirt_node& inner)
-{
-    if (inner.skip & MIRT_NODE_EMPTY) return true;
-    for (int k = 0; k < 3; k++)
-        if (!(outer.bmin[k] <= inner.bmin[k] && outer.bmax[k] >= inner.bmax[k])) return false;
-    return true;
-}
-
 // is_inner / closes / is_live: three arrays of nn + 1 ints, zeroed; tested: ns + 1 bytes, zeroed
 __global__ void nodes_kernel(const mirt_node* nd, int nn, const uint32_t* aos, int ns, uint32_t* dnodes, int* is_inner,
                              int* closes, int* is_live, uint8_t* tested, int* ctl)
@@ -248,7 +122,7 @@ __global__ void nodes_kernel(const mirt_node* nd, int nn, const uint32_t* aos, i
     if (i >= nn) return;
     const mirt_node n = nd[i];
     const bool inner = n.sphere < 0, empty = (n.skip & MIRT_NODE_EMPTY) != 0;
-    const bool live = !inner && !empty && n.sphere < ns;
+    const bool live = hitable(n, ns);
     uint32_t g[4] = {0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u};
     if (!inner && n.sphere < ns)
         for (int k = 0; k < 4; k++) g[k] = aos[5 * (size_t)n.sphere + k];
@@ -304,11 +178,11 @@ __global__ void depth_kernel(const mirt_node* nd, int nn, int ns, const int* is_
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nn) return;
     const mirt_node n = nd[i];
-    const int depth = prefix(is_inner, tsum, i) - prefix(closes, tsum + tiles, i + 1);
+    const int depth = scan_prefix(is_inner, tsum, i) - scan_prefix(closes, tsum + tiles, i + 1);
     ndepth[i] = (uint8_t)min(max(depth, 0), 255);
     if (n.sphere < 0) global_max(&ctl[kDepth], depth + 1);
-    if (n.sphere >= 0 && !(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns) {
-        const int k = prefix(is_live, tsum + 2 * (size_t)tiles, i);
+    if (hitable(n, ns)) {
+        const int k = scan_prefix(is_live, tsum + 2 * (size_t)tiles, i);
         if (k < nn) compact[k] = n.sphere;
     }
 }
@@ -326,25 +200,11 @@ __device__ void set_child(const mirt_node* nd, int nn, int ns, const int* is_inn
                           uint32_t c, uint32_t* slot, uint32_t* ref_out)
 {
     const uint32_t ci = live_node(nd, nn, ns, c);
-    const mirt_node n = nd[ci == kPNone ? c : ci];
-    float box[6] = {n.bmin[0], n.bmin[1], n.bmin[2], n.bmax[0], n.bmax[1], n.bmax[2]};
-    uint32_t ref = kPNone;
-    if (ci != kPNone) {
-        if (n.skip & MIRT_NODE_EMPTY) {
-            ref = kPNone;
-        } else if (n.sphere >= 0) {
-            ref = n.sphere >= ns ? kPNone : (kPLeaf | (uint32_t)n.sphere);
-        } else {
-            ref = 1u + (uint32_t)prefix(is_inner, tsum, (int)ci);
-        }
-        if (grow > 0.0 && ref != kPNone && !(ref & kPLeaf))
-            for (int a = 0; a < 3; a++) {
-                box[a] = next_down((float)((double)box[a] - grow));
-                box[3 + a] = next_up((float)((double)box[3 + a] + grow));
-            }
-    }
+    const bool inner = ci != kPNone && nd[ci].sphere < 0;
+    const uint32_t pidx = inner ? 1u + (uint32_t)scan_prefix(is_inner, tsum, (int)ci) : kPNone;
+    float box[6];
+    *ref_out = pnode_child(nd, ns, grow, c, ci, pidx, box);
     for (int k = 0; k < 6; k++) slot[k] = __float_as_uint(box[k]);
-    *ref_out = ref;
 }
 
 // thread i < nn: the PNode of inner node i; thread nn: PNode 0, the virtual parent of the root
@@ -364,7 +224,7 @@ __global__ void pnodes_kernel(const mirt_node* nd, int nn, int ns, const int* is
     } else {
         const mirt_node n = nd[i];
         if (n.sphere >= 0 || i + 1 >= nn) return;
-        at = 1u + (uint32_t)prefix(is_inner, tsum, i);
+        at = 1u + (uint32_t)scan_prefix(is_inner, tsum, i);
         set_child(nd, nn, ns, is_inner, tsum, grow, (uint32_t)i + 1u, &w[0], &w[12]);
         const uint32_t r = skip_of(nd[i + 1]);
         if (r < (uint32_t)nn) set_child(nd, nn, ns, is_inner, tsum, grow, r, &w[6], &w[13]);
@@ -377,40 +237,6 @@ __global__ void pnodes_kernel(const mirt_node* nd, int nn, int ns, const int* is
 }
 
 // ---- HNodes (scene_layout.cpp build_hnodes), one level per launch
-
-// the (up to four) slots of HNode(y): scene_layout.cpp's cut[], in its order
-__device__ int compute_cut(const mirt_node* nd, int nn, int ns, uint32_t y, uint32_t* cut)
-{
-    int m = 0;
-    if (y + 1 >= (uint32_t)nn) return 0;
-    uint32_t ci = live_node(nd, nn, ns, y + 1);
-    if (ci != kPNone) cut[m++] = ci;
-    ci = live_node(nd, nn, ns, skip_of(nd[y + 1]));
-    if (ci != kPNone) cut[m++] = ci;
-    for (int step = 0; step < nn && m < 4; step++) {
-        int best = -1;
-        float best_area = -1.0f;
-        for (int j = 0; j < m; j++) {
-            const mirt_node n = nd[cut[j]];
-            if (n.sphere >= 0) continue;
-            const float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-            const float area = dx * dy + dy * dz + dz * dx;
-            if (area > best_area || best < 0) {
-                best = j;
-                best_area = area;
-            }
-        }
-        if (best < 0) break;
-        const uint32_t c = cut[best];
-        cut[best] = cut[--m];
-        if (c + 1 >= (uint32_t)nn) break;
-        ci = live_node(nd, nn, ns, c + 1);
-        if (ci != kPNone) cut[m++] = ci;
-        ci = live_node(nd, nn, ns, skip_of(nd[c + 1]));
-        if (ci != kPNone) cut[m++] = ci;
-    }
-    return m;
-}
 
 struct HOut {
     uint32_t* hnodes;   // 16 words each
@@ -426,14 +252,7 @@ __device__ void fill_slot(const mirt_node* nd, int ns, const uint32_t* aos, doub
                           uint32_t* slot, uint32_t* next_h, uint32_t* next_l, int* ctl)
 {
     const mirt_node n = nd[ci];
-    for (int a = 0; a < 3; a++) {
-        float lo = n.bmin[a], hi = n.bmax[a];
-        if (grow > 0.0) {
-            lo = next_down((float)((double)lo - grow));
-            hi = next_up((float)((double)hi + grow));
-        }
-        slot[a] = half_down(lo) | (half_up(hi) << 16);
-    }
+    hnode_slot_box(n, grow, slot);
     uint32_t ref = kPNone;
     if (n.skip & MIRT_NODE_EMPTY) {
         ref = kPNone;
@@ -494,13 +313,13 @@ __global__ void hcount_kernel(const mirt_node* nd, int nn, int ns, const uint32_
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= cnt) return;
     uint32_t cut[4];
-    const int m = compute_cut(nd, nn, ns, haux[2 * ((size_t)hoff + j)], cut);
+    const int m = hnode_cut(nd, nn, ns, haux[2 * ((size_t)hoff + j)], cut);
     int ni = 0, nl = 0;
     for (int k = 0; k < 4; k++)
         if (k < m) {
             const mirt_node n = nd[cut[k]];
             if (n.sphere < 0) ni++;
-            else if (!(n.skip & MIRT_NODE_EMPTY) && n.sphere < ns) nl++;
+            else if (hitable(n, ns)) nl++;
         }
     n_inner[j] = ni;
     n_leaf[j] = nl;
@@ -517,9 +336,9 @@ __global__ void hfill_kernel(const mirt_node* nd, int nn, int ns, const uint32_t
     const uint32_t h = hoff + (uint32_t)j;
     if (h >= o.cap_h) return;
     uint32_t cut[4];
-    const int m = compute_cut(nd, nn, ns, o.haux[2 * (size_t)h], cut);
-    uint32_t next_h = hoff + (uint32_t)cnt + (uint32_t)prefix(n_inner, tsum, j);
-    uint32_t next_l = leaf_base + (uint32_t)prefix(n_leaf, tsum + tiles, j);
+    const int m = hnode_cut(nd, nn, ns, o.haux[2 * (size_t)h], cut);
+    uint32_t next_h = hoff + (uint32_t)cnt + (uint32_t)scan_prefix(n_inner, tsum, j);
+    uint32_t next_l = leaf_base + (uint32_t)scan_prefix(n_leaf, tsum + tiles, j);
     uint32_t w[16];
     for (int k = 0; k < 16; k++) w[k] = (k & 3) == 3 ? kPNone : 0u;
     for (int k = 0; k < 4; k++)
@@ -529,28 +348,6 @@ __global__ void hfill_kernel(const mirt_node* nd, int nn, int ns, const uint32_t
 }
 
 // ---- host side
-
-int hip_fail(hipError_t e, const char* what)
-{
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return MIRT_E_DEVICE;
-}
-
-#define HIP_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
-inline unsigned blocks(size_t items, int per) { return (unsigned)((items + (size_t)per - 1) / (size_t)per); }
-
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 
 // the arrays of a scene being made: freed unless the ctx took them
 struct Pending {
@@ -563,13 +360,6 @@ struct Pending {
             if (p) (void)hipFree(p);
     }
 };
-
-float bits_float(int b)
-{
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
 
 }  // namespace
 
@@ -612,7 +402,7 @@ int mirt::layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int n
         orphan_kernel<<<gn, kBlock, 0, s>>>(d_nodes, nn, ns, tested, ctl);
     }
     scan_tiles_kernel<<<dim3((unsigned)tiles, 3), kBlock, 0, s>>>(flags, pad, nn + 1, fsum, tiles);
-    scan_sums_kernel<<<3, kSumBlock, 0, s>>>(fsum, tiles, ctl + kTotInner);
+    scan_sums_kernel<kSumBlock><<<3, kSumBlock, 0, s>>>(fsum, tiles, ctl + kTotInner);
     if (nn > 0) {
         depth_kernel<<<gn, kBlock, 0, s>>>(d_nodes, nn, ns, flags, flags + pad, flags + 2 * pad, fsum, tiles,
                                            (uint8_t*)sc.ndepth, compact, ctl);
@@ -632,12 +422,9 @@ int mirt::layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int n
     sc.r_max = nests ? bits_float(h[kRMax]) : 0.0f;
     sc.c_max = nests ? bits_float(h[kCMax]) : 0.0f;
     sc.encloses = nests && !h[kOrphan];
-    double cb = sc.c_max;
-    cb = std::max(cb, (double)bits_float(h[kBoxMax]));
-    cb = cb * (1.0 + 0x1p-10) + 0x1p-10;
-    const bool bounded = sc.encloses && cb < 6.0e4;
-    sc.o_bound = bounded ? (float)cb : 0.0f;
-    const double grow = bounded ? cb * 0x1p-19 : 0.0;
+    const LayoutBound bound = layout_bound(sc.c_max, bits_float(h[kBoxMax]), sc.encloses);
+    sc.o_bound = bound.o_bound;
+    const double grow = bound.grow;
     sc.ordered = nn > 0 && !h[kNotMono] && h[kDepth] + 2 <= 64;
     sc.num_nodes = nn;
     sc.num_spheres = ns;
@@ -675,7 +462,7 @@ int mirt::layout_device(mirt_ctx* c, hipStream_t s, const uint32_t* d_aos, int n
         const int ltiles = (int)(((size_t)cnt + kTile - 1) / kTile);
         hcount_kernel<<<gl, kBlock, 0, s>>>(d_nodes, nn, ns, (const uint32_t*)sc.haux, hoff, cnt, lvl, lvl + pad);
         scan_tiles_kernel<<<dim3((unsigned)ltiles, 2), kBlock, 0, s>>>(lvl, pad, cnt, lsum, ltiles);
-        scan_sums_kernel<<<2, kSumBlock, 0, s>>>(lsum, ltiles, ctl + kLvlInner);
+        scan_sums_kernel<kSumBlock><<<2, kSumBlock, 0, s>>>(lsum, ltiles, ctl + kLvlInner);
         hfill_kernel<<<gl, kBlock, 0, s>>>(d_nodes, nn, ns, d_aos, grow, ho, hoff, cnt, leaf_base, lvl, lvl + pad, lsum,
                                            ltiles, ctl);
         HIP_TRY(hipGetLastError());

@@ -12,6 +12,7 @@
 
 #include "internal.h"
 #include "layout.h"
+#include "layout_rules.h"
 
 using namespace mirt;
 
@@ -32,7 +33,7 @@ bool orphan_phantoms(const mirt_node* nd, int nn, int ns)
 {
     std::vector<char> tested((size_t)ns + 1, 0);
     for (int i = 0; i < nn; i++)
-        if (nd[i].sphere >= 0 && nd[i].sphere < ns && !(nd[i].skip & MIRT_NODE_EMPTY)) tested[nd[i].sphere] = 1;
+        if (hitable(nd[i], ns)) tested[nd[i].sphere] = 1;
     for (int i = 0; i < nn; i++)
         if (nd[i].sphere >= 0 && nd[i].sphere < ns && (nd[i].skip & MIRT_NODE_EMPTY) && !tested[nd[i].sphere])
             return true;
@@ -49,12 +50,6 @@ bool tree_encloses(const mirt_sphere* sp, int ns, const mirt_node* nd, int nn, f
         rm = std::max(rm, r);
         cm = std::max(cm, std::max(std::fabs(c[0]), std::max(std::fabs(c[1]), std::fabs(c[2]))) + r);
     }
-    auto holds = [](const mirt_node& outer, const mirt_node& inner) {
-        if (inner.skip & MIRT_NODE_EMPTY) return true;  // +inf/-inf box, no sphere
-        for (int k = 0; k < 3; k++)
-            if (!(outer.bmin[k] <= inner.bmin[k] && outer.bmax[k] >= inner.bmax[k])) return false;
-        return true;
-    };
     for (int i = 0; i < nn; i++) {
         const mirt_node& n = nd[i];
         if (n.skip & MIRT_NODE_EMPTY) continue;
@@ -66,53 +61,14 @@ bool tree_encloses(const mirt_sphere* sp, int ns, const mirt_node* nd, int nn, f
             for (int k = 0; k < 3; k++)
                 if (!(n.bmin[k] <= c[k] - r && n.bmax[k] >= c[k] + r)) return false;
         } else {
-            const uint32_t left = (uint32_t)i + 1, right = nd[left].skip & MIRT_SKIP_MASK;
-            if (!holds(n, nd[left]) || (right < (uint32_t)nn && right < (n.skip & MIRT_SKIP_MASK) && !holds(n, nd[right])))
+            const uint32_t left = (uint32_t)i + 1, right = skip_of(nd[left]);
+            if (!holds(n, nd[left]) || (right < (uint32_t)nn && right < skip_of(n) && !holds(n, nd[right])))
                 return false;
         }
     }
     *r_max = rm;
     *c_max = cm;
     return true;
-}
-
-// A leaf the fast walks may drop: the &spheres[N] sentinel (never hits), or
-// a 0-sphere leaf. hit.c:96-97 does test a 0-sphere leaf's sphere (its box,
-// create_empty_aabb's, always passes): spheres[start] of its range when the
-// SAH fallback split left it empty (mid == start: the first sphere of its
-// sibling's range), spheres[end] when it split right (mid == end: a sphere
-// of some LATER subtree). Dropping it is exact when that sphere is the
-// tested sphere of a non-empty leaf (upload checks this, `orphan_phantoms`;
-// otherwise only the reference-order DFS walk runs) and the ray reaches that
-// leaf whenever it hits the sphere: the leaf's box holds the sphere's box
-// fl(c -+ r) (checked, tree_encloses), the reference slab test is monotone
-// under containment, so this rests on ONE assumption -- hit.c:49-82's
-// division slab test passes the box fl(c -+ r) of every sphere that
-// hit.c:19-39 reports hit. Both are exact-rounding computations of the same
-// chord; tests/test_gpu_parity.py test_phantom_grazing_rays aims grazing rays
-// at the spheres of both kinds of 0-sphere leaf and compares the fast walks
-// with the DFS walk and the oracle.
-bool dead_leaf(const mirt_node* nd, uint32_t i, int ns)
-{
-    return nd[i].sphere >= 0 && ((nd[i].skip & MIRT_NODE_EMPTY) || nd[i].sphere >= ns);
-}
-
-// The node a walk may take in place of flat node ci: an inner node one of
-// whose children is dead adds nothing but its box test, which its live
-// child's (nested, hence stricter) box test implies -- so the chains of
-// one-sided splits the reference's SAH fallback builds (bvh.c:139-141,
-// runs of nodes each with a 0-sphere leaf beside the rest of the range)
-// collapse to the subtree that can hit. kPNone: nothing below can hit.
-uint32_t live_node(const mirt_node* nd, uint32_t ci, int ns)
-{
-    for (;;) {
-        if (nd[ci].sphere >= 0) return dead_leaf(nd, ci, ns) ? kPNone : ci;
-        const uint32_t l = ci + 1, r = nd[ci + 1].skip & MIRT_SKIP_MASK;
-        const bool dl = dead_leaf(nd, l, ns), dr = dead_leaf(nd, r, ns);
-        if (dl && dr) return kPNone;
-        if (!dl && !dr) return ci;
-        ci = dl ? r : l;
-    }
 }
 
 // PNode layout (layout.h) of a validated flat tree. Returns whether ordered
@@ -132,34 +88,8 @@ bool build_pnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, st
         if (nd[i].sphere < 0) pidx[i] = np++;
     pn.assign(np, PNode{});
     auto set_child = [&](PNode& p, int k, uint32_t c) {
-        const uint32_t ci = live_node(nd, c, ns);
-        if (ci == kPNone) {  // nothing below can hit: an empty slot
-            float* slot = k ? p.c1 : p.c0;
-            std::memcpy(slot, nd[c].bmin, sizeof nd[c].bmin);
-            std::memcpy(slot + 3, nd[c].bmax, sizeof nd[c].bmax);
-            (k ? p.ref1 : p.ref0) = kPNone;
-            return;
-        }
-        const mirt_node& n = nd[ci];
-        float* slot = k ? p.c1 : p.c0;
-        uint32_t ref = pidx[ci];
-        std::memcpy(slot, n.bmin, sizeof n.bmin);
-        std::memcpy(slot + 3, n.bmax, sizeof n.bmax);
-        if (n.skip & MIRT_NODE_EMPTY) {
-            ref = kPNone;  // a 0-sphere leaf: passes, never hits
-        } else if (n.sphere >= 0) {
-            if (n.sphere >= ns || (uint32_t)n.sphere > kPIndex) {
-                ref = kPNone;
-            } else {
-                ref = kPLeaf | (uint32_t)n.sphere;
-            }
-        }
-        if (grow > 0.0 && ref != kPNone && !(ref & kPLeaf))
-            for (int a = 0; a < 3; a++) {
-                slot[a] = std::nextafter((float)((double)slot[a] - grow), -INFINITY);
-                slot[3 + a] = std::nextafter((float)((double)slot[3 + a] + grow), INFINITY);
-            }
-        (k ? p.ref1 : p.ref0) = ref;
+        const uint32_t ci = live_node(nd, nn, ns, c);
+        (k ? p.ref1 : p.ref0) = pnode_child(nd, ns, grow, c, ci, ci == kPNone ? kPNone : pidx[ci], k ? p.c1 : p.c0);
     };
     pn[0].ref0 = pn[0].ref1 = kPNone;
     pn[0].flat = 0xffffffffu;  // flat + 1 == 0: the whole tree
@@ -174,45 +104,17 @@ bool build_pnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, st
         if (nd[i].sphere < 0) {
             PNode& p = pn[pidx[i]];
             set_child(p, 0, (uint32_t)i + 1);
-            set_child(p, 1, nd[i + 1].skip & MIRT_SKIP_MASK);
+            set_child(p, 1, skip_of(nd[i + 1]));
             p.flat = (uint32_t)i;
-            p.end = nd[i].skip & MIRT_SKIP_MASK;
-            ends.push_back(nd[i].skip & MIRT_SKIP_MASK);
+            p.end = skip_of(nd[i]);
+            ends.push_back(skip_of(nd[i]));
             depth = std::max(depth, ends.size());
-        } else if (!(nd[i].skip & MIRT_NODE_EMPTY) && nd[i].sphere < ns) {
+        } else if (hitable(nd[i], ns)) {
             if (nd[i].sphere <= last) mono = false;
             last = nd[i].sphere;
         }
     }
     return mono && depth + 2 <= 64;
-}
-
-// fp16 bits of the largest half <= v / the smallest half >= v (a value
-// beyond the fp16 range rounds out to -inf / +inf: still a superset).
-uint16_t half_bits(float v)
-{
-    const _Float16 h = (_Float16)v;
-    uint16_t b;
-    std::memcpy(&b, &h, 2);
-    return b;
-}
-float half_value(uint16_t b)
-{
-    _Float16 h;
-    std::memcpy(&h, &b, 2);
-    return (float)h;
-}
-uint16_t half_down(float v)
-{
-    uint16_t b = half_bits(v);
-    while (half_value(b) > v) b = b == 0x0000 ? 0x8001 : (b & 0x8000) ? b + 1 : b - 1;
-    return b;
-}
-uint16_t half_up(float v)
-{
-    uint16_t b = half_bits(v);
-    while (half_value(b) < v) b = b == 0x8000 ? 0x0001 : (b & 0x8000) ? b - 1 : b + 1;
-    return b;
 }
 
 // HNode layout (layout.h) of a validated flat tree: HNode 0 holds the root;
@@ -229,22 +131,17 @@ void build_hnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, st
     lgeo.clear();
     lbox.clear();
     std::vector<uint32_t> todo;  // inner nodes waiting for their HNode: HNode 1 + i is todo[i]
+    // a slot's reference is numbered as slots are filled (scene_device.hip's fill_slot takes its numbers from
+    // prefix sums and guards its arrays' capacity): the two numberings stay apart
     auto fill = [&](size_t hi, int k, uint32_t c) {
         HNode& h = hn[hi];
-        const uint32_t ci = live_node(nd, c, ns);
+        const uint32_t ci = live_node(nd, nn, ns, c);
         if (ci == kPNone) {
             h.slot[k].ref = kPNone;
             return;
         }
         const mirt_node& n = nd[ci];
-        for (int a = 0; a < 3; a++) {
-            float lo = n.bmin[a], hi = n.bmax[a];
-            if (grow > 0.0) {   // rounded outward again: the float of lo - grow may lie above it
-                lo = std::nextafter((float)((double)lo - grow), -INFINITY);
-                hi = std::nextafter((float)((double)hi + grow), INFINITY);
-            }
-            h.slot[k].box[a] = (uint32_t)half_down(lo) | ((uint32_t)half_up(hi) << 16);
-        }
+        hnode_slot_box(n, grow, h.slot[k].box);
         uint32_t ref;
         if (n.skip & MIRT_NODE_EMPTY) {
             ref = kPNone;
@@ -275,37 +172,9 @@ void build_hnodes(const mirt_node* nd, int nn, const mirt_sphere* sp, int ns, st
         HNode h{};
         for (int k = 0; k < 4; k++) h.slot[k].ref = kPNone;
         hn.push_back(h);
-        aux.push_back(HAux{y, nd[y].skip & MIRT_SKIP_MASK});
-        // the four slots: y's live children, then the inner slot with the
-        // largest box replaced by its two live children while a slot is
-        // free (every slot stays inside y's flat subtree, which HAux walks)
+        aux.push_back(HAux{y, skip_of(nd[y])});
         uint32_t cut[4];
-        int m = 0;
-        auto add = [&](uint32_t c) {
-            const uint32_t ci = live_node(nd, c, ns);
-            if (ci != kPNone) cut[m++] = ci;
-        };
-        add(y + 1);
-        add(nd[y + 1].skip & MIRT_SKIP_MASK);
-        while (m < 4) {
-            int best = -1;
-            float best_area = -1.0f;
-            for (int j = 0; j < m; j++) {
-                const mirt_node& n = nd[cut[j]];
-                if (n.sphere >= 0) continue;
-                const float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
-                const float area = dx * dy + dy * dz + dz * dx;
-                if (area > best_area || best < 0) {
-                    best = j;
-                    best_area = area;
-                }
-            }
-            if (best < 0) break;
-            const uint32_t c = cut[best];
-            cut[best] = cut[--m];
-            add(c + 1);
-            add(nd[c + 1].skip & MIRT_SKIP_MASK);
-        }
+        const int m = hnode_cut(nd, nn, ns, y, cut);
         for (int k = 0; k < m; k++) fill(hn.size() - 1, k, cut[k]);
     }
 }
@@ -338,22 +207,17 @@ void build_scene_layout(const mirt_sphere* spheres, int ns, const mirt_node* nod
         d.skip = nodes[i].skip;
         std::memcpy(&d.geo, &geo[nodes[i].sphere >= 0 ? nodes[i].sphere : ns], sizeof d.geo);  // float4 under HIP
     }
-    // the margin-free box tests (bounce walks, camera packets): C bounds every box coordinate and every sphere point
-    // (so every bounce-ray origin, up to rounding: the margin 2^-10 C + 2^-10),
-    // and the slot boxes grow by 2^-19 C (trace.h slab_cons_fast<BND>)
-    double cb = out.c_max;
+    float box_max = 0.0f;  // the largest finite |coordinate| of a non-empty node's box
     for (int i = 0; i < nn; i++) {
         if (nodes[i].skip & MIRT_NODE_EMPTY) continue;
         for (int a = 0; a < 3; a++)
             for (float v : {nodes[i].bmin[a], nodes[i].bmax[a]})
-                if (std::isfinite(v)) cb = std::max(cb, (double)std::fabs(v));
+                if (std::isfinite(v)) box_max = std::max(box_max, std::fabs(v));
     }
-    cb = cb * (1.0 + 0x1p-10) + 0x1p-10;
-    const bool bounded = out.encloses && cb < 6.0e4;   // fp16 range: the grown boxes stay finite
-    out.o_bound = bounded ? (float)cb : 0.0f;   // 0: every bounce ray takes the exact test
-    out.ordered = build_pnodes(nodes, nn, spheres, ns, out.pnodes, bounded ? cb * 0x1p-19 : 0.0);
-    build_hnodes(nodes, nn, spheres, ns, out.hnodes, out.haux, out.leaf_geo, out.leaf_box,
-                 bounded ? cb * 0x1p-19 : 0.0);
+    const LayoutBound bound = layout_bound(out.c_max, box_max, out.encloses);
+    out.o_bound = bound.o_bound;
+    out.ordered = build_pnodes(nodes, nn, spheres, ns, out.pnodes, bound.grow);
+    build_hnodes(nodes, nn, spheres, ns, out.hnodes, out.haux, out.leaf_geo, out.leaf_box, bound.grow);
     const size_t nl = out.leaf_box.size();
     out.leaf_box_off = (sizeof(Geo4) * nl + 255) & ~(size_t)255;
     // node depths (pre-order: the children of inner node i are i + 1 and the

@@ -5,13 +5,17 @@
 // mirt_bvh_refit_flat on identity, moved and invalid inputs: builder trees with
 // stuck groups and 0-sphere leaves, a tree built over [0, n - 1), trees that
 // index the never-hit sentinel, non-monotone and malformed trees, every bad
-// `end`. Exit 0 = every check held and no sanitizer fired (they abort on a
+// `end`; and csrc/tree.h's sphere_declined on the inputs the device paths hand
+// to the host. Exit 0 = every check held and no sanitizer fired (they abort on a
 // finding).
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "../../cs201_sah-bvh_ray_tracer_amd/csrc/tree.h"
 #include "../../include/mirt.h"
 
 static int failures = 0;
@@ -162,6 +166,21 @@ int main()
         std::vector<mirt_node> bad = {node(-1, 3), node(0, 2), node(9, 3)};
         CHECK(refit(bad, s, 8) == MIRT_E_INVALID);
         CHECK(std::strstr(mirt_last_error(), "malformed node 2") != nullptr);
+    }
+    {   // the spheres the device refit and build hand to the host (csrc/tree.h sphere_declined)
+        auto declined = [](float x, float y, float z, float r) {
+            uint32_t w[4];
+            const float f[4] = {x, y, z, r};
+            std::memcpy(w, f, sizeof w);
+            return mirt::sphere_declined(w[0], w[1], w[2], w[3]);
+        };
+        const float nan = std::nanf(""), inf = HUGE_VALF;
+        CHECK(declined(nan, 5.0f, 7.0f, 1.0f));     // a NaN centre
+        CHECK(declined(3.0f, 5.0f, 7.0f, inf));     // an infinite radius
+        CHECK(declined(-0.0f, 5.0f, 7.0f, 0.0f));   // c - r == -0.0
+        CHECK(declined(3.0f, 5.0f, -0.0f, -0.0f));  // c + r == -0.0
+        CHECK(!declined(1.0f, 5.0f, 7.0f, 1.0f));   // c - r == +0.0
+        CHECK(!declined(3.0f, -5.0f, 7.0f, 0.5f));  // an ordinary sphere
     }
     if (failures) {
         std::fprintf(stderr, "san_refit: %d check(s) failed\n", failures);
