@@ -211,6 +211,7 @@ SIGNATURES = [
     ("mirt_bvh_quality_flat", I, [P, I, I, P]),
     ("mirt_scene_quality", I, [P, P]),
     ("mirt_scene_update_device", I, [P, P, I, I, I, C.c_double, P, P, P]),
+    ("mirt_scene_update_device_ptr", I, [P, P, I, I, I, C.c_double, P, P, P]),
     ("mirt_shard_rows", I, [P, P]),
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),
@@ -222,6 +223,8 @@ SIGNATURES = [
     ("mirt_host_unregister", I, [P]),
     ("mirt_accum_download", I, [P, P, C.c_size_t]),
     ("mirt_ctx_share_accum", I, [P, P]),
+    ("mirt_ctx_share_scene", I, [P, P]),
+    ("mirt_ctx_scene_id", C.c_uint64, [P]),
     ("mirt_trace_rays", I, [P, P, I, I, I, C.c_uint64, C.c_uint32, P]),
     ("mirt_trace_rays_at", I, [P, P, I, I, I, C.c_uint64, C.c_uint32, C.c_uint32, P]),
     ("mirt_camera_rays_uv", I, [P, P, I, I, P, I, P]),
@@ -270,6 +273,9 @@ SIGNATURES = [
     ("mirt_multi_get_option", I, [P, I]),
     ("mirt_multi_scene_upload", I, [P, P, I, P]),
     ("mirt_multi_scene_upload_flat", I, [P, P, I, P, I]),
+    ("mirt_multi_scene_build_device", I, [P, P, I, I, I, I, P]),
+    ("mirt_multi_scene_refit_device", I, [P, P, I, I]),
+    ("mirt_multi_scene_update_device", I, [P, P, I, I, I, C.c_double, P, P, P]),
     ("mirt_multi_render_frame", I, [P, P, P, P]),
     ("mirt_multi_render_frame_async", I, [P, P, P, P]),
     ("mirt_multi_render_frames_async", I, [P, P, P, I, I, C.POINTER(P)]),

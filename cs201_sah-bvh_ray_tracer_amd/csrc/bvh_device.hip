@@ -112,6 +112,24 @@ __global__ void prep_kernel(const uint32_t* aos, int n, float4* geo, uint32_t* c
     nof[i] = 0;
 }
 
+// The device-source entry of a build (mirt_scene_update_device_ptr's rebuild):
+// the `total` 20-byte spheres at src copied to the build's scratch with each
+// colour word replaced by the sphere's index, the colours saved aside. One
+// thread per 32-bit word, so loads and stores stay coalesced.
+__global__ void tag_kernel(const uint32_t* __restrict__ src, size_t words, uint32_t* __restrict__ aos,
+                           uint32_t* __restrict__ colour)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= words) return;
+    const size_t sphere = i / 5;
+    uint32_t v = src[i];
+    if (i - 5 * sphere == 4) {
+        colour[sphere] = v;
+        v = (uint32_t)sphere;
+    }
+    aos[i] = v;
+}
+
 __global__ void finish_kernel(const float4* geo, const uint32_t* col, int n, uint32_t* aos)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -650,9 +668,12 @@ int run_partition(BuildState& st, hipStream_t s, int cur, int n, int off, int cn
 // of the n of them from `first` on is built (leaf indices count from sphere0)
 // and stays in st.out, *out_count nodes; st.aos then holds all `total` spheres
 // with that range reordered. Enqueued, not waited for: download() or the
-// caller synchronises. *declined = 1: nothing was built, the host builder must run
+// caller synchronises. *declined = 1: nothing was built, the host builder must run.
+// d_src set: the spheres come from device memory instead, tagged by tag_kernel
+// (d_colour[total] receives their colours).
 int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int total, int first, int n, int sphere0,
-                 int depth, int* out_count, int* declined, int* levels_out)
+                 int depth, int* out_count, int* declined, int* levels_out, const uint32_t* d_src = nullptr,
+                 uint32_t* d_colour = nullptr)
 {
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
     *declined = 0;
@@ -664,8 +685,13 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
     int h_ctl[kCtlWords] = {0, 0, 0, 0};
     int cur = 0;
     HIP_TRY(hipMemsetAsync(ctl, 0, kCtlWords * 4, s));
-    if (total > 0)
+    if (total > 0 && d_src) {
+        const size_t words = 5 * (size_t)total;
+        tag_kernel<<<blocks(words, kBlock), kBlock, 0, s>>>(d_src, words, (uint32_t*)st.aos.p, d_colour);
+        HIP_TRY(hipGetLastError());
+    } else if (total > 0) {
         HIP_TRY(hipMemcpyAsync(st.aos.p, spheres, (size_t)total * sizeof(mirt_sphere), hipMemcpyHostToDevice, s));
+    }
     uint32_t* aos = (uint32_t*)st.aos.p + 5 * (size_t)first;  // the range being built
     HIP_TRY(hipEventRecord(st.ev0, s));
     if (n > 0) {
@@ -769,13 +795,15 @@ int download(mirt_ctx* c, BuildState& st, mirt_sphere* spheres, int n, int count
 
 namespace mirt {
 
-int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start, int end, int depth,
-                   ResidentTree* out, int* declined)
+namespace {
+int build_resident_from(mirt_ctx* c, const mirt_sphere* spheres, const uint32_t* d_src, uint32_t* d_colour, int total,
+                        int start, int end, int depth, ResidentTree* out, int* declined)
 {
     BuildState* st = nullptr;
     if (int rc = get_state(c, &st)) return rc;
     int count = 0, levels = 0;
-    if (int rc = device_build(c, *st, spheres, total, start, end - start, start, depth, &count, declined, &levels)) {
+    if (int rc = device_build(c, *st, spheres, total, start, end - start, start, depth, &count, declined, &levels,
+                              d_src, d_colour)) {
         (void)hipStreamSynchronize((hipStream_t)mirt_ctx_stream(c));
         return rc;
     }
@@ -784,6 +812,20 @@ int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start
     out->num_nodes = count;
     out->levels = levels;
     return MIRT_OK;
+}
+}  // namespace
+
+int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start, int end, int depth,
+                   ResidentTree* out, int* declined)
+{
+    return build_resident_from(c, spheres, nullptr, nullptr, total, start, end, depth, out, declined);
+}
+
+int build_resident_tagged(mirt_ctx* c, const void* d_spheres, int total, int start, int end, int depth,
+                          uint32_t* d_colour, ResidentTree* out, int* declined)
+{
+    return build_resident_from(c, nullptr, (const uint32_t*)d_spheres, d_colour, total, start, end, depth, out,
+                               declined);
 }
 
 int build_resident_ms(mirt_ctx* c, float* ms)

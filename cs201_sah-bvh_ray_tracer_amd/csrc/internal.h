@@ -55,6 +55,12 @@ struct ResidentTree {
 };
 int build_resident(mirt_ctx* c, const mirt_sphere* spheres, int total, int start, int end, int depth,
                    ResidentTree* out, int* declined);
+// The same from `total` spheres in device memory (read on the ctx's stream,
+// not written): the build runs on a copy whose colour words hold the spheres'
+// indices -- what mirt_scene_update_device builds on to learn its permutation
+// -- and d_colour[total] (device) receives the spheres' own colours.
+int build_resident_tagged(mirt_ctx* c, const void* d_spheres, int total, int start, int end, int depth,
+                          uint32_t* d_colour, ResidentTree* out, int* declined);
 int build_resident_ms(mirt_ctx* c, float* ms);
 // render.hip: the scene arrays of a ctx (csrc/layout.h has the element types),
 // all device allocations the ctx owns, and the scalars that go with them.
@@ -67,10 +73,12 @@ struct DeviceScene {
     bool encloses = false, ordered = false, leaf_big = false;
     float r_max = 0.0f, c_max = 0.0f, o_bound = 0.0f;
 };
-// Installs `sc` in the ctx, which owns the arrays from here on: waits for the
-// ctx's enqueued frames, frees the scene it held (num_spheres = -1 until the
-// new one is in place), then takes the pointers and scalars.
+// Installs `sc` (complete on the device) in the ctx's scene slot, for every ctx
+// that shares it; the slot owns the arrays from here on. The scene it held is
+// freed once the frames enqueued on it have finished (mirt_ctx_share_scene).
 int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc);
+// the two ctxs render one scene slot
+bool ctx_shares_scene(const mirt_ctx* a, const mirt_ctx* b);
 void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st);
 // What a refit reads of the resident scene (refit_device.hip): the public 32-B
 // tree and the node depths on the device, and the scalars. false: no scene.
@@ -94,7 +102,8 @@ int layout_device(mirt_ctx* c, ihipStream_t* stream, const uint32_t* d_aos, int 
 int quality_device(ihipStream_t* stream, const mirt_node* d_nodes, int nn, int ns, mirt_tree_quality* out,
                    const char* fn);
 // render.hip: the cost of the tree the last mirt_scene_update_device installed
-// (false: none -- every install drops it, only that call sets it again).
+// in the ctx's scene slot (false: none -- every install drops it, only that
+// call sets it again).
 bool ctx_base_cost(const mirt_ctx* c, double* cost);
 void ctx_set_base_cost(mirt_ctx* c, double cost);
 // [p, p + bytes) is ONE page-locked host range (mirt_host_alloc /

@@ -286,6 +286,25 @@ int fail_multi(mirt_multi* m, const std::string& why)
     return MIRT_E_DEVICE;
 }
 
+// Every rank thread has issued lane `li`'s launch (bounded by the deadline
+// counted from t0).
+int wait_lane_issued(mirt_multi* m, int li, std::chrono::steady_clock::time_point t0)
+{
+    using clk = std::chrono::steady_clock;
+    Lane& L = m->lanes[li];
+    for (long polls = 0; L.issued->load(std::memory_order_acquire) < m->n; polls++) {
+        if (m->timeout_ms > 0 && std::chrono::duration<double, std::milli>(clk::now() - t0).count() > m->timeout_ms)
+            return fail_multi(m, "lane " + std::to_string(li) + ": the rank threads did not issue the launch within " +
+                                     std::to_string(m->timeout_ms) + " ms (MIRT_MULTI_OPT_TIMEOUT_MS); communicators "
+                                     "aborted, the object is unusable");
+        if (polls < 2000)
+            std::this_thread::yield();
+        else
+            std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    return MIRT_OK;
+}
+
 // Wait for lane `li`'s launch on every rank: every rank thread has issued
 // it, then each rank's completion event, polled against the deadline (no
 // unbounded hipStreamSynchronize). An issue error is returned once the work
@@ -300,16 +319,7 @@ int wait_lane(mirt_multi* m, int li)
     auto over = [&]() {
         return m->timeout_ms > 0 && std::chrono::duration<double, std::milli>(clk::now() - t0).count() > m->timeout_ms;
     };
-    for (long polls = 0; L.issued->load(std::memory_order_acquire) < m->n; polls++) {
-        if (over())
-            return fail_multi(m, "lane " + std::to_string(li) + ": the rank threads did not issue the launch within " +
-                                     std::to_string(m->timeout_ms) + " ms (MIRT_MULTI_OPT_TIMEOUT_MS); communicators "
-                                     "aborted, the object is unusable");
-        if (polls < 2000)
-            std::this_thread::yield();
-        else
-            std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
+    if (int rc = wait_lane_issued(m, li, t0)) return rc;
     for (int r = 0; r < m->n; r++) {
         for (long polls = 0;; polls++) {
             const hipError_t e = hipEventQuery(L.done[r]);
@@ -778,6 +788,97 @@ int enqueue(mirt_multi* m, int li, const mirt_camera* cam, const mirt_frame_desc
     return MIRT_OK;
 }
 
+// Every rank thread has issued the launches already handed to it (bounded by
+// MIRT_MULTI_OPT_TIMEOUT_MS): those threads read their contexts' scene slots,
+// which a scene call on the caller's thread is about to change. The launches
+// themselves are NOT waited for.
+int wait_issued(mirt_multi* m)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int li = 0; li < (int)m->lanes.size(); li++)
+        if (m->lanes[li].pending)
+            if (int rc = wait_lane_issued(m, li, t0)) return rc;
+    return MIRT_OK;
+}
+
+// The leader of every distinct device: its first owning context, lowest lane
+// then lowest rank (so leaders[0] is on rank 0's device).
+std::vector<mirt_ctx*> device_leaders(mirt_multi* m)
+{
+    std::vector<mirt_ctx*> leaders;
+    std::vector<int> seen;
+    for (Lane& L : m->lanes) {
+        if (!L.owns_ctx) continue;
+        for (int r = 0; r < m->n; r++)
+            if (std::find(seen.begin(), seen.end(), m->dev[r]) == seen.end()) {
+                seen.push_back(m->dev[r]);
+                leaders.push_back(L.ctx[r]);
+            }
+    }
+    return leaders;
+}
+
+// All owned contexts of a device join their leader's scene slot. Joining waits
+// for the joining context's frames, so where any context still has to join,
+// the lanes are waited for first (bounded); an object that already shares
+// changes nothing here and waits for nothing.
+int share_per_device(mirt_multi* m, const std::vector<mirt_ctx*>& leaders)
+{
+    bool shared = true;
+    for (Lane& L : m->lanes)
+        if (L.owns_ctx)
+            for (int r = 0; r < m->n; r++) {
+                mirt_ctx* lead = nullptr;
+                for (mirt_ctx* c : leaders)
+                    if (ctx_device(c) == m->dev[r]) lead = c;
+                if (L.ctx[r] != lead && !ctx_shares_scene(L.ctx[r], lead)) shared = false;
+            }
+    if (shared) return MIRT_OK;
+    for (int l = 0; l < (int)m->lanes.size(); l++)
+        if (int rc = wait_lane(m, l)) return rc;
+    for (Lane& L : m->lanes)
+        if (L.owns_ctx)
+            for (int r = 0; r < m->n; r++)
+                for (mirt_ctx* lead : leaders)
+                    if (ctx_device(lead) == m->dev[r] && L.ctx[r] != lead)
+                        if (int rc = mirt_ctx_share_scene(L.ctx[r], lead)) return rc;
+    return MIRT_OK;
+}
+
+// The checks and the preparation the three _device scene calls share: the
+// object, then (need_scene) every leader's resident scene of `ns` spheres --
+// all reported before anything is changed -- then the issue of the launches in
+// flight and the sharing.
+int scene_call_begin(mirt_multi* m, bool need_scene, int ns, std::vector<mirt_ctx*>& leaders, const char* fn)
+{
+    if (m->failed) return failed_status(m, fn);
+    leaders = device_leaders(m);
+    if (need_scene)
+        for (mirt_ctx* c : leaders) {
+            ResidentScene rs{};
+            if (!ctx_resident_scene(c, &rs)) {
+                set_error("%s: no scene uploaded", fn);
+                return MIRT_E_NOSCENE;
+            }
+            if (ns != rs.num_spheres) {
+                set_error("%s: %d spheres for a resident scene of %d", fn, ns, rs.num_spheres);
+                return MIRT_E_INVALID;
+            }
+        }
+    if (int rc = wait_issued(m)) return rc;
+    return share_per_device(m, leaders);
+}
+
+// A scene call failed on device k's leader: before any device installed
+// (k == 0) the object is as it was; later the devices disagree, and the object
+// fails as after a timeout.
+int scene_call_failed(mirt_multi* m, size_t k, int rc, const char* fn)
+{
+    if (k == 0) return rc;
+    return fail_multi(m, std::string(fn) + ": device " + std::to_string(k) + " of the object failed (" +
+                             mirt_last_error() + ") after earlier devices installed the scene; the object is unusable");
+}
+
 bool multi_ok(mirt_multi* m, const char* fn)
 {
     if (!m) set_error("%s: null mirt_multi", fn);
@@ -1073,8 +1174,11 @@ int mirt_multi_scene_upload(mirt_multi* m, const mirt_sphere* spheres, int num_s
         if (int rc = wait_lane(m, l)) return rc;
     for (Lane& L : m->lanes)
         if (L.owns_ctx)
-            for (mirt_ctx* c : L.ctx)
+            for (mirt_ctx* c : L.ctx) {
+                // a private slot again (after a _device scene call the contexts of a device share one)
+                if (int rc = mirt_ctx_share_scene(c, nullptr)) return rc;
                 if (int rc = mirt_scene_upload(c, spheres, num_spheres, root)) return rc;
+            }
     return MIRT_OK;
 }
 
@@ -1086,9 +1190,84 @@ int mirt_multi_scene_upload_flat(mirt_multi* m, const mirt_sphere* spheres, int 
         if (int rc = wait_lane(m, l)) return rc;
     for (Lane& L : m->lanes)
         if (L.owns_ctx)
-            for (mirt_ctx* c : L.ctx)
+            for (mirt_ctx* c : L.ctx) {
+                // a private slot again (after a _device scene call the contexts of a device share one)
+                if (int rc = mirt_ctx_share_scene(c, nullptr)) return rc;
                 if (int rc = mirt_scene_upload_flat(c, spheres, num_spheres, nodes, num_nodes)) return rc;
+            }
     return MIRT_OK;
+}
+
+int mirt_multi_scene_build_device(mirt_multi* m, const mirt_sphere* spheres, int num_spheres, int start, int end,
+                                  int depth, mirt_sphere* reordered)
+try {
+    const char* fn = "mirt_multi_scene_build_device";
+    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+    if (!spheres || num_spheres < 0 || start < 0 || end < start || end > num_spheres) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    std::vector<mirt_ctx*> leaders;
+    if (int rc = scene_call_begin(m, false, num_spheres, leaders, fn)) return rc;
+    for (size_t k = 0; k < leaders.size(); k++)
+        if (int rc = mirt_scene_build_device(leaders[k], spheres, num_spheres, start, end, depth,
+                                             k == 0 ? reordered : nullptr))
+            return scene_call_failed(m, k, rc, fn);
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("mirt_multi_scene_build_device: out of host memory");
+    return MIRT_E_NOMEM;
+}
+
+int mirt_multi_scene_refit_device(mirt_multi* m, const mirt_sphere* spheres, int num_spheres, int end)
+try {
+    const char* fn = "mirt_multi_scene_refit_device";
+    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+    if (num_spheres < 0 || (num_spheres > 0 && !spheres) || end < 0 || end > num_spheres) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    std::vector<mirt_ctx*> leaders;
+    if (int rc = scene_call_begin(m, true, num_spheres, leaders, fn)) return rc;
+    for (size_t k = 0; k < leaders.size(); k++)
+        if (int rc = mirt_scene_refit_device(leaders[k], spheres, num_spheres, end, nullptr))
+            return scene_call_failed(m, k, rc, fn);
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("mirt_multi_scene_refit_device: out of host memory");
+    return MIRT_E_NOMEM;
+}
+
+int mirt_multi_scene_update_device(mirt_multi* m, const mirt_sphere* spheres, int num_spheres, int start, int end,
+                                   double max_decay, mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
+try {
+    const char* fn = "mirt_multi_scene_update_device";
+    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+    if (num_spheres < 0 || (num_spheres > 0 && !spheres) || start < 0 || end < start || end > num_spheres) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    std::vector<mirt_ctx*> leaders;
+    if (int rc = scene_call_begin(m, true, num_spheres, leaders, fn)) return rc;
+    mirt_update_result first;
+    for (size_t k = 0; k < leaders.size(); k++) {
+        mirt_update_result res;
+        if (int rc = mirt_scene_update_device(leaders[k], spheres, num_spheres, start, end, max_decay,
+                                              k == 0 ? reordered : nullptr, k == 0 ? perm : nullptr, &res))
+            return scene_call_failed(m, k, rc, fn);
+        if (k == 0) first = res;
+        // the builds are bit-identical, so every device reaches the same decision
+        if (res.rebuilt != first.rebuilt)
+            return fail_multi(m, std::string(fn) + ": device " + std::to_string(k) +
+                                     " of the object decided otherwise than the first (rebuilt " +
+                                     std::to_string(res.rebuilt) + " against " + std::to_string(first.rebuilt) +
+                                     "); the object is unusable");
+    }
+    if (out) *out = first;
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("mirt_multi_scene_update_device: out of host memory");
+    return MIRT_E_NOMEM;
 }
 
 int mirt_multi_render_frames_async(mirt_multi* m, const mirt_camera* cam, const mirt_frame_desc* fd, int nframes,

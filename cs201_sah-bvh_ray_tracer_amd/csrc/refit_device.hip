@@ -164,6 +164,13 @@ __global__ void perm_kernel(uint32_t* aos, int ns, const uint32_t* colour, int32
     if (from < (uint32_t)ns) aos[5 * (size_t)i + 4] = colour[from];
 }
 
+// mirt_scene_update_device_ptr's refit branch: the identity permutation, written on the device
+__global__ void iota_kernel(int32_t* perm, int ns)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < ns) perm[i] = i;
+}
+
 // ---- host side
 
 // The refit kernels on stream s: d_tree[nn] from the resident tree and the spheres at d_aos. *verdict = 0: d_tree is
@@ -346,14 +353,18 @@ void identity(const mirt_sphere* spheres, int ns, mirt_sphere* reordered, int32_
         for (int32_t i = 0; i < ns; i++) perm[i] = i;
 }
 
-// mirt_scene_update_device: refit into the scratch tree, measure it, then install either it or a
-// rebuild. Nothing is installed, and the ctx's base cost is not touched, before the decision's own tree is complete.
-int update(mirt_ctx* c, const mirt_sphere* spheres, int ns, int start, int end, double max_decay,
-           mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
+// mirt_scene_update_device[_ptr]: refit into the scratch tree, measure it, then install either
+// it or a rebuild. Nothing is installed, and the slot's base cost is not touched, before the decision's own tree is
+// complete. Host form: `spheres`, `reordered`, `perm` in host memory. Device form (d_spheres set, or ptr_form with
+// ns == 0): the spheres are read on the ctx's stream and d_reordered / d_perm written there; on the paths the
+// kernels accept no sphere, colour or permutation crosses the host link.
+int update(mirt_ctx* c, const mirt_sphere* spheres, const void* d_spheres, bool ptr_form, int ns, int start, int end,
+           double max_decay, mirt_sphere* reordered, int32_t* perm, void* d_reordered, int32_t* d_perm_out,
+           mirt_update_result* out, const char* fn)
 try {
-    const char* fn = "mirt_scene_update_device";
     ResidentScene rs{};
-    const bool args_ok = ns >= 0 && (ns == 0 || spheres) && start >= 0 && end >= start && end <= ns;
+    const bool args_ok = ns >= 0 && (ns == 0 || spheres || d_spheres) && start >= 0 && end >= start && end <= ns &&
+                         !(d_reordered && d_reordered == d_spheres);
     if (int rc = resident_scene(c, args_ok, ns, &rs, fn)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx_device(c)));
@@ -378,7 +389,7 @@ try {
     int declined;
     {
         Refit r;
-        int rc = refit_stage(s, rs, spheres, nullptr, end, r, fn);
+        int rc = refit_stage(s, rs, spheres, d_spheres, end, r, fn);
         if (rc) return rc;
         declined = r.declined;
         const mirt_node* tree = (const mirt_node*)r.tree.p;
@@ -386,39 +397,58 @@ try {
         if (!declined && (rc = quality_device(s, tree, nn, ns, &q, fn))) return rc;
         if (!declined && !wants_rebuild(q)) {
             rc = layout_device(c, s, r.d_aos, ns, tree, nn, fn);
-            const hipError_t e = hipStreamSynchronize(s);
+            hipError_t e = hipSuccess;
+            if (!rc && ptr_form && ns > 0) {
+                if (d_reordered) e = hipMemcpyAsync(d_reordered, d_spheres, sph_bytes, hipMemcpyDeviceToDevice, s);
+                if (e == hipSuccess && d_perm_out) {
+                    iota_kernel<<<blocks((size_t)ns, kBlock), kBlock, 0, s>>>(d_perm_out, ns);
+                    e = hipGetLastError();
+                }
+            }
+            const hipError_t e2 = hipStreamSynchronize(s);
             if (rc) return rc;
-            if (e != hipSuccess) return hip_fail(e, fn);
-            identity(spheres, ns, reordered, perm);
+            if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, fn);
+            if (!ptr_form) identity(spheres, ns, reordered, perm);
             res.installed = q;
             res.on_device = 1;
         } else if (!declined) {
-            const std::vector<mirt_sphere> copy = indexed(spheres, ns);
+            // the spheres' own colours, then the permutation: one allocation
+            DevMem extra;
+            HIP_TRY(hipMalloc(&extra.p, std::max<size_t>((size_t)ns * 8, 8)));
+            uint32_t* d_colour = (uint32_t*)extra.p;
+            int32_t* d_perm = (int32_t*)(d_colour + ns);
+            std::vector<mirt_sphere> copy;
+            std::vector<uint32_t> colour;
             ResidentTree built{};
-            if ((rc = build_resident(c, copy.data(), ns, start, end, 0, &built, &declined))) return rc;
+            if (ptr_form) {
+                rc = build_resident_tagged(c, d_spheres, ns, start, end, 0, d_colour, &built, &declined);
+            } else {
+                copy = indexed(spheres, ns);
+                rc = build_resident(c, copy.data(), ns, start, end, 0, &built, &declined);
+            }
+            if (rc) return rc;
             if (!declined) {
-                // the spheres' own colours, then the permutation: one allocation
-                DevMem extra;
-                std::vector<uint32_t> colour((size_t)ns);
-                for (int i = 0; i < ns; i++) std::memcpy(&colour[(size_t)i], &spheres[i].color, 4);
-                hipError_t e = hipMalloc(&extra.p, std::max<size_t>((size_t)ns * 8, 8));
-                uint32_t* d_colour = (uint32_t*)extra.p;
-                int32_t* d_perm = (int32_t*)(d_colour + ns);
-                if (e == hipSuccess && ns > 0) {
+                hipError_t e = hipSuccess;
+                if (!ptr_form && ns > 0) {
+                    colour.resize((size_t)ns);
+                    for (int i = 0; i < ns; i++) std::memcpy(&colour[(size_t)i], &spheres[i].color, 4);
                     e = hipMemcpyAsync(d_colour, colour.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s);
-                    if (e == hipSuccess) {
-                        perm_kernel<<<blocks((size_t)ns, kBlock), kBlock, 0, s>>>((uint32_t*)built.aos, ns, d_colour,
-                                                                                   d_perm);
-                        e = hipGetLastError();
-                    }
+                }
+                if (e == hipSuccess && ns > 0) {
+                    perm_kernel<<<blocks((size_t)ns, kBlock), kBlock, 0, s>>>((uint32_t*)built.aos, ns, d_colour,
+                                                                               d_perm);
+                    e = hipGetLastError();
                 }
                 mirt_tree_quality qb;
                 if (e == hipSuccess) rc = quality_device(s, built.nodes, built.num_nodes, ns, &qb, fn);
                 if (e == hipSuccess && !rc) rc = layout_device(c, s, built.aos, ns, built.nodes, built.num_nodes, fn);
-                if (e == hipSuccess && !rc && reordered && ns > 0)
-                    e = hipMemcpyAsync(reordered, built.aos, sph_bytes, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess && !rc && perm && ns > 0)
-                    e = hipMemcpyAsync(perm, d_perm, (size_t)ns * 4, hipMemcpyDeviceToHost, s);
+                void* const to_reordered = ptr_form ? d_reordered : (void*)reordered;
+                void* const to_perm = ptr_form ? (void*)d_perm_out : (void*)perm;
+                const hipMemcpyKind kind = ptr_form ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+                if (e == hipSuccess && !rc && to_reordered && ns > 0)
+                    e = hipMemcpyAsync(to_reordered, built.aos, sph_bytes, kind, s);
+                if (e == hipSuccess && !rc && to_perm && ns > 0)
+                    e = hipMemcpyAsync(to_perm, d_perm, (size_t)ns * 4, kind, s);
                 const hipError_t e2 = hipStreamSynchronize(s);  // `copy`, `colour` and `extra` are free again
                 if (rc) return rc;
                 if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, fn);
@@ -433,9 +463,15 @@ try {
     }
     if (declined) {
         // the host refit, the host measure, then the host upload or the host build and upload: the same result
-        std::vector<mirt_sphere> unused;
+        // (device form: the spheres are fetched, and reordered and perm uploaded)
+        std::vector<mirt_sphere> fetched, h_reordered;
+        std::vector<int32_t> h_perm;
+        if (ptr_form) {
+            if (d_reordered) reordered = (h_reordered.resize((size_t)std::max(ns, 1)), h_reordered.data());
+            if (d_perm_out) perm = (h_perm.resize((size_t)std::max(ns, 1)), h_perm.data());
+        }
         std::vector<mirt_node> nodes;
-        if (int rc = host_refit(s, rs, &spheres, nullptr, end, unused, nodes)) return rc;
+        if (int rc = host_refit(s, rs, &spheres, d_spheres, end, fetched, nodes)) return rc;
         mirt_tree_quality q;
         if (int rc = mirt_bvh_quality_flat(nodes.data(), nn, ns, &q)) return rc;
         if (!wants_rebuild(q)) {
@@ -463,6 +499,10 @@ try {
             res.installed = qb;
             new_base = qb.cost;
         }
+        if (ptr_form && ns > 0) {
+            if (d_reordered) HIP_TRY(hipMemcpy(d_reordered, reordered, sph_bytes, hipMemcpyHostToDevice));
+            if (d_perm_out) HIP_TRY(hipMemcpy(d_perm_out, perm, (size_t)ns * 4, hipMemcpyHostToDevice));
+        }
         res.on_device = 0;
     }
     ctx_set_base_cost(c, new_base);
@@ -470,7 +510,7 @@ try {
     if (out) *out = res;
     return MIRT_OK;
 } catch (const std::bad_alloc&) {
-    set_error("mirt_scene_update_device: out of host memory");
+    set_error("%s: out of host memory", fn);
     return MIRT_E_NOMEM;
 }
 
@@ -481,7 +521,15 @@ extern "C" {
 int mirt_scene_update_device(mirt_ctx* c, const mirt_sphere* spheres, int num_spheres, int start, int end,
                              double max_decay, mirt_sphere* reordered, int32_t* perm, mirt_update_result* out)
 {
-    return update(c, spheres, num_spheres, start, end, max_decay, reordered, perm, out);
+    return update(c, spheres, nullptr, false, num_spheres, start, end, max_decay, reordered, perm, nullptr, nullptr, out,
+                  "mirt_scene_update_device");
+}
+
+int mirt_scene_update_device_ptr(mirt_ctx* c, const void* d_spheres, int num_spheres, int start, int end,
+                                 double max_decay, void* d_reordered, int32_t* d_perm, mirt_update_result* out)
+{
+    return update(c, nullptr, d_spheres, true, num_spheres, start, end, max_decay, nullptr, nullptr, d_reordered,
+                  d_perm, out, "mirt_scene_update_device_ptr");
 }
 
 int mirt_scene_refit_device(mirt_ctx* c, const mirt_sphere* spheres, int num_spheres, int end, mirt_node* out_nodes)

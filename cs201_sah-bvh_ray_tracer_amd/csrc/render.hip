@@ -1520,6 +1520,49 @@ struct AccumShare {
 
 
 
+// One resident scene: the nine device arrays and the scalars that go with
+// them. Immutable once installed; freed only when no slot holds it and every
+// stream that may still read it has passed the events in `readers`.
+struct Scene {
+    int refs = 0;               // slots that hold it
+    uint64_t id = 0;            // mirt_ctx_scene_id: stamped at install, process-wide
+    DNode* d_nodes = nullptr;
+    mirt_node* d_nodes32 = nullptr;
+    float4* d_geo = nullptr;
+    uint32_t* d_color = nullptr;
+    int num_nodes = 0, num_spheres = -1;
+    bool prune_ok = false;      // the uploaded tree's boxes enclose their subtrees
+    PNode* d_pnodes = nullptr;  // ordered-walk layout of the tree
+    bool ordered_ok = false;    // leaves in DFS order hold increasing sphere indices, depth < 63
+    HNode* d_hnodes = nullptr;  // four-wide layout (per-lane walks)
+    HAux* d_haux = nullptr;
+    char* d_leaves = nullptr;   // leaf spheres (float4 each), then at leaf_box_off the leaf boxes (LeafBox each)
+    size_t leaf_box_off = 0;
+    uint32_t num_hnodes = 0;
+    uint32_t num_pnodes = 0, num_leaves = 0;  // read back by mirt_scene_resident_layout
+    uint32_t wide_root = 0;     // HNode a four-wide walk starts at (DevScene::wide_root)
+    uint8_t* d_ndepth = nullptr;  // depth of every flat node (BVH overlay colours)
+    float r_max = 0.0f, c_max = 0.0f;
+    float o_bound = 0.0f;       // the bounce walks' origin bound the HNode boxes were grown for
+    bool leaf_big = false;      // the four-wide tree (HNodes + leaves) exceeds the chip's L2
+    // one event per member stream of every slot that gave the scene up,
+    // recorded behind the frames that slot's members had enqueued on it
+    std::vector<hipEvent_t> readers;
+};
+
+// The scene slot of a ctx: one per ctx by default;
+// mirt_ctx_share_scene lets the ctxs of one device render ONE resident scene.
+// An install through any member replaces `cur` for all of them; the replaced
+// scene waits in `retired` until its readers' events have passed (checked at
+// the slot's later installs, waited for when the slot itself goes).
+struct SceneSlot {
+    Scene* cur = nullptr;
+    std::vector<mirt_ctx*> members;
+    std::vector<Scene*> retired;
+    double base_cost = 0.0;     // mirt_scene_update_device: the cost of the tree it last installed
+    bool have_base_cost = false;  // dropped by every install of a scene
+};
+
 struct mirt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1543,12 +1586,7 @@ struct mirt_ctx {
     bool slab_guard = false;
     hipStream_t last_stream = nullptr;
     bool launched = false;
-    // scene (replicated per device, uploaded once)
-    DNode* d_nodes = nullptr;
-    mirt_node* d_nodes32 = nullptr;
-    float4* d_geo = nullptr;
-    uint32_t* d_color = nullptr;
-    int num_nodes = 0, num_spheres = -1;
+    SceneSlot* slot = nullptr;  // the scene it renders (own, or shared: mirt_ctx_share_scene)
     // frame buffers owned by the ctx (blocking API)
     uint32_t* d_out = nullptr;
     size_t out_cap = 0;
@@ -1564,22 +1602,9 @@ struct mirt_ctx {
     int block_waves = 4;  // waves (8x8 tiles) per workgroup
     int defer = 1;        // trace zero-component camera rays in leading waves
     int prune = 1;              // closest-hit pruning (trace.h Prune), FAST slab only
-    bool prune_ok = false;      // the uploaded tree's boxes enclose their subtrees
-    PNode* d_pnodes = nullptr;  // ordered-walk layout of the tree
-    bool ordered_ok = false;    // leaves in DFS order hold increasing sphere indices, depth < 63
     int ordered = 1;            // ordered (nearer-child-first) walks where the tree admits them
-    HNode* d_hnodes = nullptr;  // four-wide layout (per-lane walks)
-    HAux* d_haux = nullptr;
-    char* d_leaves = nullptr;   // leaf spheres (float4 each), then at leaf_box_off the leaf boxes (LeafBox each)
-    size_t leaf_box_off = 0;
-    uint32_t num_hnodes = 0;
-    uint32_t num_pnodes = 0, num_leaves = 0;  // read back by mirt_scene_resident_layout
-    uint32_t wide_root = 0;     // HNode a four-wide walk starts at (DevScene::wide_root)
-    uint8_t* d_ndepth = nullptr;  // depth of every flat node (BVH overlay colours)
     uint32_t* d_overlay = nullptr;  // BVH overlay: per-pixel last line in draw order
     size_t overlay_cap = 0;
-    float r_max = 0.0f, c_max = 0.0f;
-    float o_bound = 0.0f;       // the bounce walks' origin bound the HNode boxes were grown for
     int bounce_threshold = 20;  // wavefront: shade finished rays once fewer lanes walk (swept: profiles/r02thr_threshold_sweep.txt)
     int bounce_blocks = 0;      // wavefront: persistent workgroups (set in mirt_create)
     int bounce_blocks_opt = 0;  // MIRT_OPT_BOUNCE_BLOCKS override (0: occupancy x CUs)
@@ -1587,7 +1612,6 @@ struct mirt_ctx {
     int quad_batch = 1;                          // small BVH batches one ray per quad (intersect_quad_kernel)
     int leaf_batch_opt = 2;                        // MIRT_OPT_LEAF_BATCH: 0 off, 1 on, 2 auto (leaf_big)
     int zero_copy = 1;          // MIRT_OPT_ZERO_COPY: blocking frames into page-locked memory written in place
-    bool leaf_big = false;      // the four-wide tree (HNodes + leaves) exceeds the chip's L2
     void* d_queue = nullptr;    // wavefront: {count, head} + bounce records
     size_t queue_cap = 0;
     bool lone_frame = false;    // mirt_render_frame's frame: the first bounces queued in tile order
@@ -1605,8 +1629,6 @@ struct mirt_ctx {
     bool have_scene_stats = false;
     mirt_refit_stats refit_stats{};  // of the last mirt_scene_refit_device[_ptr]
     bool have_refit_stats = false;
-    double base_cost = 0.0;     // mirt_scene_update_device: the cost of the tree it last installed
-    bool have_base_cost = false;  // dropped by every install of a scene
 };
 
 namespace {
@@ -1634,6 +1656,107 @@ int ensure(void** p, size_t* cap, size_t bytes)
     return MIRT_OK;
 }
 
+// The scene a ctx renders: its slot's, or the empty one (num_spheres < 0: no
+// scene) before the first install.
+const Scene kNoScene{};
+const Scene* scene_of(const mirt_ctx* c)
+{
+    return c->slot && c->slot->cur ? c->slot->cur : &kNoScene;
+}
+
+void scene_free(Scene* sn)
+{
+    for (void* p : {(void*)sn->d_nodes, (void*)sn->d_nodes32, (void*)sn->d_geo, (void*)sn->d_color, (void*)sn->d_pnodes,
+                    (void*)sn->d_hnodes, (void*)sn->d_haux, (void*)sn->d_leaves, (void*)sn->d_ndepth})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : sn->readers) (void)hipEventDestroy(ev);
+    delete sn;
+}
+
+// Frees the slot's retired scenes whose readers have all passed (wait: waits
+// for them first -- a bounded wait, the frames were enqueued long ago).
+void slot_reap(SceneSlot* sl, bool wait)
+{
+    size_t kept = 0;
+    for (Scene* sn : sl->retired) {
+        bool idle = true;
+        for (hipEvent_t ev : sn->readers) {
+            if (wait) (void)hipEventSynchronize(ev);
+            else if (hipEventQuery(ev) != hipSuccess) idle = false;
+        }
+        if (!idle) (void)hipGetLastError();  // hipErrorNotReady is no error of a later launch
+        if (idle) scene_free(sn);
+        else sl->retired[kept++] = sn;
+    }
+    sl->retired.resize(kept);
+}
+
+// The slot gives up its scene: every frame its members have enqueued so far
+// (on their own streams, or on a caller's stream -- `done` follows those) may
+// still read it, so each member's stream gets an event behind them. The scene
+// no slot holds any longer moves to this slot's retired list.
+void slot_drop_scene(SceneSlot* sl)
+{
+    Scene* sn = sl->cur;
+    sl->cur = nullptr;
+    sl->have_base_cost = false;
+    if (!sn) return;
+    for (mirt_ctx* m : sl->members) {
+        // a member with nothing in flight reads nothing: no event (the loop of
+        // blocking frames then frees the replaced scene at once, as it always has)
+        bool busy = hipStreamQuery(m->stream) != hipSuccess;
+        if (m->launched && m->last_stream != m->stream && hipEventQuery(m->done) != hipSuccess) {
+            (void)hipStreamWaitEvent(m->stream, m->done, 0);
+            busy = true;
+        }
+        if (!busy) continue;
+        (void)hipGetLastError();  // hipErrorNotReady is no error of a later launch
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess &&
+            hipEventRecord(ev, m->stream) == hipSuccess) {
+            sn->readers.push_back(ev);
+        } else {
+            if (ev) (void)hipEventDestroy(ev);
+            (void)hipStreamSynchronize(m->stream);  // no event to be had: the frames themselves
+        }
+    }
+    if (--sn->refs == 0) sl->retired.push_back(sn);
+}
+
+// The ctx leaves its slot (its own enqueued frames have been waited for). The
+// last member takes the slot with it.
+void slot_leave(mirt_ctx* c)
+{
+    SceneSlot* sl = c->slot;
+    c->slot = nullptr;
+    if (!sl) return;
+    sl->members.erase(std::remove(sl->members.begin(), sl->members.end(), c), sl->members.end());
+    if (!sl->members.empty()) return;
+    slot_drop_scene(sl);
+    slot_reap(sl, true);
+    delete sl;
+}
+
+uint64_t next_scene_id()
+{
+    static std::mutex mu;
+    static uint64_t last = 0;
+    std::lock_guard<std::mutex> lock(mu);
+    return ++last;
+}
+
+// `sn` (complete on the device, refs == 0) becomes the scene of the ctx's
+// slot, for every member.
+void slot_install(mirt_ctx* c, Scene* sn)
+{
+    SceneSlot* sl = c->slot;
+    slot_drop_scene(sl);
+    slot_reap(sl, false);
+    sn->id = next_scene_id();
+    sn->refs = 1;
+    sl->cur = sn;
+}
+
 // MIRT_OPT_CONFIRM_ONCE in effect for the uploaded scene. Automatic (2): on up
 // to kConfirmOnceLeaves leaves. Measured (MEASUREMENTS.md §D, round 8): at
 // 10k spheres (1080p and 4K) every round is ahead of the parent; at 100k the
@@ -1645,7 +1768,7 @@ int ensure(void** p, size_t* cap, size_t bytes)
 constexpr uint32_t kConfirmOnceLeaves = 1u << 15;
 static bool confirm_once(const mirt_ctx* c)
 {
-    return c->confirm_once == 1 || (c->confirm_once == 2 && c->num_leaves <= kConfirmOnceLeaves);
+    return c->confirm_once == 1 || (c->confirm_once == 2 && scene_of(c)->num_leaves <= kConfirmOnceLeaves);
 }
 
 // MIRT_OPT_LEAF_BATCH: the bounce walk loads a step's passing leaf spheres
@@ -1654,17 +1777,18 @@ static bool confirm_once(const mirt_ctx* c)
 // miss: 4K/1M +9%, 1080p/10k and 100k -9% / -6%
 bool leaf_batch(const mirt_ctx* c)
 {
-    return c->leaf_batch_opt == 1 || (c->leaf_batch_opt == 2 && c->leaf_big);
+    return c->leaf_batch_opt == 1 || (c->leaf_batch_opt == 2 && scene_of(c)->leaf_big);
 }
 
 DevScene dev_scene(const mirt_ctx* c)
 {
-    const bool prune = c->prune && c->prune_ok;
-    const bool ordered = prune && c->ordered && c->ordered_ok && c->fast_slab;
-    return DevScene{c->d_nodes, c->d_nodes32, c->d_geo, c->d_color, (uint32_t)c->num_nodes, c->num_spheres,
-                    prune, c->r_max, c->c_max, c->d_pnodes, ordered, c->d_hnodes, c->d_haux,
-                    (const float4*)c->d_leaves, (const LeafBox*)(c->d_leaves + c->leaf_box_off), ordered,
-                    ordered ? c->num_hnodes : 0u, c->wide_root, c->o_bound};
+    const Scene* sn = scene_of(c);
+    const bool prune = c->prune && sn->prune_ok;
+    const bool ordered = prune && c->ordered && sn->ordered_ok && c->fast_slab;
+    return DevScene{sn->d_nodes, sn->d_nodes32, sn->d_geo, sn->d_color, (uint32_t)sn->num_nodes, sn->num_spheres,
+                    prune, sn->r_max, sn->c_max, sn->d_pnodes, ordered, sn->d_hnodes, sn->d_haux,
+                    (const float4*)sn->d_leaves, (const LeafBox*)(sn->d_leaves + sn->leaf_box_off), ordered,
+                    ordered ? sn->num_hnodes : 0u, sn->wide_root, sn->o_bound};
 }
 
 AccumShare* accum_new(int device)
@@ -1764,7 +1888,7 @@ bool ctx_ok(mirt_ctx* c, bool need_scene, const char* fn)
         set_error("%s: null context", fn);
         return false;
     }
-    if (need_scene && c->num_spheres < 0) {
+    if (need_scene && scene_of(c)->num_spheres < 0) {
         set_error("%s: no scene uploaded", fn);
         return false;
     }
@@ -1821,7 +1945,7 @@ int launch_render(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_ac
 bool camera_bounded(const mirt_ctx* c, const FrameConst& f)
 {
     const float o = std::max(std::fabs(f.px), std::max(std::fabs(f.py), std::fabs(f.pz)));
-    return origin_within_4c(c->o_bound, o);
+    return origin_within_4c(scene_of(c)->o_bound, o);
 }
 
 int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s, bool timed,
@@ -1995,7 +2119,7 @@ int launch_brute(mirt_ctx* c, int n)
     int rc = ensure((void**)&c->d_keys, &c->keys_cap, sizeof(unsigned long long) * (size_t)n);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_keys, 0xff, sizeof(unsigned long long) * (size_t)n, c->stream));
-    const int ns = c->num_spheres;
+    const int ns = scene_of(c)->num_spheres;
     if (ns <= 0) return MIRT_OK;
     const int bx = (n + 255) / 256;
     const int want = std::max(1, 8 * std::max(1, c->num_cus) / bx);
@@ -2046,7 +2170,9 @@ int mirt_create(int device, mirt_ctx** out)
     if (e == hipSuccess) e = hipMalloc((void**)&c->d_counts, sizeof(mirt_counts));
     if (e == hipSuccess) {
         c->acc = accum_new(device);
-        if (!c->acc) e = hipErrorOutOfMemory;
+        c->slot = new (std::nothrow) SceneSlot();
+        if (!c->acc || !c->slot) e = hipErrorOutOfMemory;
+        if (c->slot) c->slot->members.push_back(c);
     }
     if (e == hipSuccess) {
         int cus = 0, per_cu = 0;
@@ -2072,13 +2198,13 @@ void mirt_destroy(mirt_ctx* c)
     // a share that lives on must not keep a pending fold of this ctx's slab
     if (c->acc && c->acc->refs > 1 && c->acc->pend_ctx == c) (void)accum_materialize(c->acc, c->stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->launched && c->last_stream != c->stream) (void)hipEventSynchronize(c->done);  // a frame on a caller's stream
     if (c->slab_guard) (void)hipEventSynchronize(c->slab_free);   // another stream's read of the slab
     accum_release(c->acc);
     mirt::build_state_free(c->build);
-    for (void* p : {(void*)c->d_nodes, (void*)c->d_nodes32, (void*)c->d_geo, (void*)c->d_color, (void*)c->d_out,
-                    c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue, (void*)c->d_keys, (void*)c->d_pnodes,
-                    (void*)c->d_hnodes, (void*)c->d_haux, (void*)c->d_leaves, (void*)c->d_ndepth,
-                    (void*)c->d_overlay})
+    slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
+    for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
+                    (void*)c->d_keys, (void*)c->d_overlay})
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2106,54 +2232,56 @@ try {
     // the device arrays: `alloc` bytes allocated at *dst (0: the array goes
     // `off` bytes into the allocation the row before made), `bytes` copied
     const size_t n1 = nn > 0 ? nn : 1, nl = lay.leaf_box.size();
+    Scene* sn = new Scene();
     const struct {
         void** dst;
         size_t alloc, off;
         const void* src;
         size_t bytes;
     } up[] = {
-        {(void**)&c->d_nodes, sizeof(DNode) * n1, 0, lay.dnodes.data(), sizeof(DNode) * (size_t)nn},
-        {(void**)&c->d_nodes32, sizeof(mirt_node) * n1, 0, nodes, sizeof(mirt_node) * (size_t)nn},
-        {(void**)&c->d_geo, sizeof(float4) * lay.geo.size(), 0, lay.geo.data(), sizeof(float4) * lay.geo.size()},
-        {(void**)&c->d_color, sizeof(uint32_t) * lay.color.size(), 0, lay.color.data(),
+        {(void**)&sn->d_nodes, sizeof(DNode) * n1, 0, lay.dnodes.data(), sizeof(DNode) * (size_t)nn},
+        {(void**)&sn->d_nodes32, sizeof(mirt_node) * n1, 0, nodes, sizeof(mirt_node) * (size_t)nn},
+        {(void**)&sn->d_geo, sizeof(float4) * lay.geo.size(), 0, lay.geo.data(), sizeof(float4) * lay.geo.size()},
+        {(void**)&sn->d_color, sizeof(uint32_t) * lay.color.size(), 0, lay.color.data(),
          sizeof(uint32_t) * lay.color.size()},
-        {(void**)&c->d_pnodes, sizeof(PNode) * lay.pnodes.size(), 0, lay.pnodes.data(),
+        {(void**)&sn->d_pnodes, sizeof(PNode) * lay.pnodes.size(), 0, lay.pnodes.data(),
          sizeof(PNode) * lay.pnodes.size()},
-        {(void**)&c->d_hnodes, sizeof(HNode) * lay.hnodes.size(), 0, lay.hnodes.data(),
+        {(void**)&sn->d_hnodes, sizeof(HNode) * lay.hnodes.size(), 0, lay.hnodes.data(),
          sizeof(HNode) * lay.hnodes.size()},
-        {(void**)&c->d_haux, sizeof(HAux) * lay.haux.size(), 0, lay.haux.data(), sizeof(HAux) * lay.haux.size()},
-        {(void**)&c->d_leaves, lay.leaf_box_off + sizeof(LeafBox) * std::max<size_t>(nl, 1), 0, lay.leaf_geo.data(),
+        {(void**)&sn->d_haux, sizeof(HAux) * lay.haux.size(), 0, lay.haux.data(), sizeof(HAux) * lay.haux.size()},
+        {(void**)&sn->d_leaves, lay.leaf_box_off + sizeof(LeafBox) * std::max<size_t>(nl, 1), 0, lay.leaf_geo.data(),
          sizeof(float4) * nl},
-        {(void**)&c->d_leaves, 0, lay.leaf_box_off, lay.leaf_box.data(), sizeof(LeafBox) * nl},
-        {(void**)&c->d_ndepth, lay.ndepth.size(), 0, lay.ndepth.data(), lay.ndepth.size()},
+        {(void**)&sn->d_leaves, 0, lay.leaf_box_off, lay.leaf_box.data(), sizeof(LeafBox) * nl},
+        {(void**)&sn->d_ndepth, lay.ndepth.size(), 0, lay.ndepth.data(), lay.ndepth.size()},
     };
-    for (const auto& u : up)
-        if (u.alloc) {
-            if (*u.dst) (void)hipFree(*u.dst);
-            *u.dst = nullptr;
-        }
-    c->num_spheres = -1;  // until every array is in place ctx_ok rejects the context
-    c->have_base_cost = false;
+    // the slot gives up the scene it held first, as this call always has: until
+    // every array is in place ctx_ok rejects the slot's contexts
+    slot_drop_scene(c->slot);
+    slot_reap(c->slot, false);
     auto put = [](void** dst, size_t alloc, size_t off, const void* src, size_t bytes) {
         if (alloc) HIP_TRY(hipMalloc(dst, alloc));
         if (bytes) HIP_TRY(hipMemcpy((char*)*dst + off, src, bytes, hipMemcpyHostToDevice));
         return (int)MIRT_OK;
     };
     for (const auto& u : up)
-        if (int rc = put(u.dst, u.alloc, u.off, u.src, u.bytes)) return rc;
-    c->num_nodes = nn;
-    c->num_spheres = ns;
-    c->num_hnodes = (uint32_t)lay.hnodes.size();
-    c->num_pnodes = (uint32_t)lay.pnodes.size();
-    c->num_leaves = (uint32_t)nl;
-    c->leaf_box_off = lay.leaf_box_off;
-    c->leaf_big = lay.leaf_big;
-    c->wide_root = lay.wide_root;
-    c->ordered_ok = lay.ordered;
-    c->prune_ok = lay.encloses;
-    c->r_max = lay.r_max;
-    c->c_max = lay.c_max;
-    c->o_bound = lay.o_bound;
+        if (int rc = put(u.dst, u.alloc, u.off, u.src, u.bytes)) {
+            scene_free(sn);
+            return rc;
+        }
+    sn->num_nodes = nn;
+    sn->num_spheres = ns;
+    sn->num_hnodes = (uint32_t)lay.hnodes.size();
+    sn->num_pnodes = (uint32_t)lay.pnodes.size();
+    sn->num_leaves = (uint32_t)nl;
+    sn->leaf_box_off = lay.leaf_box_off;
+    sn->leaf_big = lay.leaf_big;
+    sn->wide_root = lay.wide_root;
+    sn->ordered_ok = lay.ordered;
+    sn->prune_ok = lay.encloses;
+    sn->r_max = lay.r_max;
+    sn->c_max = lay.c_max;
+    sn->o_bound = lay.o_bound;
+    slot_install(c, sn);
     return MIRT_OK;
 } catch (const std::bad_alloc&) {
     set_error("mirt_scene_upload_flat: out of host memory");
@@ -2167,33 +2295,34 @@ int64_t mirt_scene_resident_layout(mirt_ctx* c, int part, void* out, size_t cap,
         return MIRT_E_INVALID;
     }
     if (!ctx_ok(c, true, "mirt_scene_resident_layout")) return MIRT_E_NOSCENE;
-    const size_t nn = (size_t)c->num_nodes, ns1 = (size_t)c->num_spheres + 1, nl = c->num_leaves;
+    const Scene* sn = scene_of(c);
+    const size_t nn = (size_t)sn->num_nodes, ns1 = (size_t)sn->num_spheres + 1, nl = sn->num_leaves;
     const void* src = nullptr;
     size_t bytes = 0;
     switch (part) {
-    case MIRT_LAYOUT_DNODES: src = c->d_nodes, bytes = sizeof(DNode) * nn; break;
-    case MIRT_LAYOUT_GEO: src = c->d_geo, bytes = sizeof(float4) * ns1; break;
-    case MIRT_LAYOUT_COLOR: src = c->d_color, bytes = sizeof(uint32_t) * ns1; break;
-    case MIRT_LAYOUT_PNODES: src = c->d_pnodes, bytes = sizeof(PNode) * c->num_pnodes; break;
-    case MIRT_LAYOUT_HNODES: src = c->d_hnodes, bytes = sizeof(HNode) * c->num_hnodes; break;
-    case MIRT_LAYOUT_HAUX: src = c->d_haux, bytes = sizeof(HAux) * c->num_hnodes; break;
-    case MIRT_LAYOUT_LEAF_GEO: src = c->d_leaves, bytes = sizeof(float4) * nl; break;
-    case MIRT_LAYOUT_LEAF_BOX: src = c->d_leaves + c->leaf_box_off, bytes = sizeof(LeafBox) * nl; break;
-    case MIRT_LAYOUT_NDEPTH: src = c->d_ndepth, bytes = std::max<size_t>(nn, 1); break;
+    case MIRT_LAYOUT_DNODES: src = sn->d_nodes, bytes = sizeof(DNode) * nn; break;
+    case MIRT_LAYOUT_GEO: src = sn->d_geo, bytes = sizeof(float4) * ns1; break;
+    case MIRT_LAYOUT_COLOR: src = sn->d_color, bytes = sizeof(uint32_t) * ns1; break;
+    case MIRT_LAYOUT_PNODES: src = sn->d_pnodes, bytes = sizeof(PNode) * sn->num_pnodes; break;
+    case MIRT_LAYOUT_HNODES: src = sn->d_hnodes, bytes = sizeof(HNode) * sn->num_hnodes; break;
+    case MIRT_LAYOUT_HAUX: src = sn->d_haux, bytes = sizeof(HAux) * sn->num_hnodes; break;
+    case MIRT_LAYOUT_LEAF_GEO: src = sn->d_leaves, bytes = sizeof(float4) * nl; break;
+    case MIRT_LAYOUT_LEAF_BOX: src = sn->d_leaves + sn->leaf_box_off, bytes = sizeof(LeafBox) * nl; break;
+    case MIRT_LAYOUT_NDEPTH: src = sn->d_ndepth, bytes = std::max<size_t>(nn, 1); break;
     default: set_error("mirt_scene_resident_layout: unknown part %d", part); return MIRT_E_INVALID;
     }
     if (info) {
-        info->encloses = c->prune_ok;
-        info->ordered = c->ordered_ok;
-        info->leaf_big = c->leaf_big;
-        info->r_max = c->r_max;
-        info->c_max = c->c_max;
-        info->o_bound = c->o_bound;
-        info->num_pnodes = c->num_pnodes;
-        info->num_hnodes = c->num_hnodes;
-        info->num_leaves = c->num_leaves;
-        info->wide_root = c->wide_root;
-        info->leaf_box_off = c->leaf_box_off;
+        info->encloses = sn->prune_ok;
+        info->ordered = sn->ordered_ok;
+        info->leaf_big = sn->leaf_big;
+        info->r_max = sn->r_max;
+        info->c_max = sn->c_max;
+        info->o_bound = sn->o_bound;
+        info->num_pnodes = sn->num_pnodes;
+        info->num_hnodes = sn->num_hnodes;
+        info->num_leaves = sn->num_leaves;
+        info->wide_root = sn->wide_root;
+        info->leaf_box_off = sn->leaf_box_off;
     }
     if (out && cap >= bytes && bytes) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2253,7 +2382,7 @@ int mirt_render_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_fra
         set_error("mirt_render_frame_device: invalid arguments");
         return MIRT_E_INVALID;
     }
-    if (fd->use_bvh && c->num_nodes == 0) {
+    if (fd->use_bvh && scene_of(c)->num_nodes == 0) {
         set_error("mirt_render_frame_device: use_bvh set but no tree uploaded");
         return MIRT_E_NOSCENE;
     }
@@ -2277,7 +2406,7 @@ int enqueue_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd
         set_error("%s: invalid arguments", fn);
         return MIRT_E_INVALID;
     }
-    if (fd->use_bvh && c->num_nodes == 0) {
+    if (fd->use_bvh && scene_of(c)->num_nodes == 0) {
         set_error("%s: use_bvh set but no tree uploaded", fn);
         return MIRT_E_NOSCENE;
     }
@@ -2362,40 +2491,37 @@ int ctx_device(const mirt_ctx* c) { return c->device; }
 BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
 {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    void** held[] = {(void**)&c->d_nodes, (void**)&c->d_nodes32, (void**)&c->d_geo, (void**)&c->d_color,
-                     (void**)&c->d_pnodes, (void**)&c->d_hnodes, (void**)&c->d_haux, (void**)&c->d_leaves,
-                     (void**)&c->d_ndepth};
-    for (void** p : held) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
+    Scene* sn = new (std::nothrow) Scene();
+    if (!sn) {
+        set_error("out of host memory");
+        return MIRT_E_NOMEM;
     }
-    c->num_spheres = -1;
-    c->have_base_cost = false;
-    c->d_nodes = (DNode*)sc.dnodes;
-    c->d_nodes32 = (mirt_node*)sc.nodes32;
-    c->d_geo = (float4*)sc.geo;
-    c->d_color = (uint32_t*)sc.color;
-    c->d_pnodes = (PNode*)sc.pnodes;
-    c->d_hnodes = (HNode*)sc.hnodes;
-    c->d_haux = (HAux*)sc.haux;
-    c->d_leaves = (char*)sc.leaves;
-    c->d_ndepth = (uint8_t*)sc.ndepth;
-    c->num_nodes = sc.num_nodes;
-    c->num_hnodes = sc.num_hnodes;
-    c->num_pnodes = sc.num_pnodes;
-    c->num_leaves = sc.num_leaves;
-    c->leaf_box_off = sc.leaf_box_off;
-    c->leaf_big = sc.leaf_big;
-    c->wide_root = sc.wide_root;
-    c->ordered_ok = sc.ordered;
-    c->prune_ok = sc.encloses;
-    c->r_max = sc.r_max;
-    c->c_max = sc.c_max;
-    c->o_bound = sc.o_bound;
-    c->num_spheres = sc.num_spheres;
+    sn->d_nodes = (DNode*)sc.dnodes;
+    sn->d_nodes32 = (mirt_node*)sc.nodes32;
+    sn->d_geo = (float4*)sc.geo;
+    sn->d_color = (uint32_t*)sc.color;
+    sn->d_pnodes = (PNode*)sc.pnodes;
+    sn->d_hnodes = (HNode*)sc.hnodes;
+    sn->d_haux = (HAux*)sc.haux;
+    sn->d_leaves = (char*)sc.leaves;
+    sn->d_ndepth = (uint8_t*)sc.ndepth;
+    sn->num_nodes = sc.num_nodes;
+    sn->num_hnodes = sc.num_hnodes;
+    sn->num_pnodes = sc.num_pnodes;
+    sn->num_leaves = sc.num_leaves;
+    sn->leaf_box_off = sc.leaf_box_off;
+    sn->leaf_big = sc.leaf_big;
+    sn->wide_root = sc.wide_root;
+    sn->ordered_ok = sc.ordered;
+    sn->prune_ok = sc.encloses;
+    sn->r_max = sc.r_max;
+    sn->c_max = sc.c_max;
+    sn->o_bound = sc.o_bound;
+    sn->num_spheres = sc.num_spheres;
+    slot_install(c, sn);
     return MIRT_OK;
 }
+bool ctx_shares_scene(const mirt_ctx* a, const mirt_ctx* b) { return a && b && a->slot == b->slot; }
 void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st)
 {
     c->scene_stats = st;
@@ -2403,8 +2529,9 @@ void ctx_set_scene_stats(mirt_ctx* c, const mirt_scene_build_stats& st)
 }
 bool ctx_resident_scene(const mirt_ctx* c, ResidentScene* out)
 {
-    if (c->num_spheres < 0) return false;
-    *out = ResidentScene{c->d_nodes32, c->d_ndepth, c->num_nodes, c->num_spheres, c->ordered_ok};
+    const Scene* sn = scene_of(c);
+    if (sn->num_spheres < 0) return false;
+    *out = ResidentScene{sn->d_nodes32, sn->d_ndepth, sn->num_nodes, sn->num_spheres, sn->ordered_ok};
     return true;
 }
 void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st)
@@ -2414,13 +2541,13 @@ void ctx_set_refit_stats(mirt_ctx* c, const mirt_refit_stats& st)
 }
 bool ctx_base_cost(const mirt_ctx* c, double* cost)
 {
-    if (c->have_base_cost) *cost = c->base_cost;
-    return c->have_base_cost;
+    if (c->slot->have_base_cost) *cost = c->slot->base_cost;
+    return c->slot->have_base_cost;
 }
 void ctx_set_base_cost(mirt_ctx* c, double cost)
 {
-    c->base_cost = cost;
-    c->have_base_cost = true;
+    c->slot->base_cost = cost;
+    c->slot->have_base_cost = true;
 }
 }  // namespace mirt
 
@@ -2646,6 +2773,47 @@ int mirt_ctx_share_accum(mirt_ctx* c, mirt_ctx* owner)
     return MIRT_OK;
 }
 
+int mirt_ctx_share_scene(mirt_ctx* c, mirt_ctx* owner)
+try {
+    if (!c) {
+        set_error("mirt_ctx_share_scene: null context");
+        return MIRT_E_INVALID;
+    }
+    if (!ctx_ok(c, false, "mirt_ctx_share_scene")) return MIRT_E_INVALID;
+    if (owner && owner->device != c->device) {
+        set_error("mirt_ctx_share_scene: ctxs on devices %d and %d", c->device, owner->device);
+        return MIRT_E_INVALID;
+    }
+    SceneSlot* next = owner && owner != c ? owner->slot : nullptr;
+    if (next == c->slot || (!next && c->slot->members.size() == 1)) return MIRT_OK;  // already so / already private
+    // c's frames enqueued so far read its old slot's scene: once they are
+    // done, that slot need not follow c's stream any longer
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+    if (!next) {
+        // a private slot again, holding the scene the group has now: the
+        // arrays stay shared (and read-only) until either slot's next install
+        next = new SceneSlot();
+        next->cur = c->slot->cur;
+        if (next->cur) next->cur->refs++;
+        next->base_cost = c->slot->base_cost;
+        next->have_base_cost = c->slot->have_base_cost;
+    }
+    next->members.reserve(next->members.size() + 1);
+    slot_leave(c);
+    next->members.push_back(c);
+    c->slot = next;
+    return MIRT_OK;
+} catch (const std::bad_alloc&) {
+    set_error("mirt_ctx_share_scene: out of host memory");
+    return MIRT_E_NOMEM;
+}
+
+uint64_t mirt_ctx_scene_id(mirt_ctx* c)
+{
+    return c ? scene_of(c)->id : 0;
+}
+
 int mirt_count_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_counts* out)
 {
     if (!ctx_ok(c, true, "mirt_count_frame")) return MIRT_E_NOSCENE;
@@ -2747,7 +2915,7 @@ int mirt_trace_rays_at(mirt_ctx* c, const mirt_ray* rays, int n, int depth, int 
         set_error("mirt_trace_rays: invalid arguments");
         return MIRT_E_INVALID;
     }
-    if (use_bvh && c->num_nodes == 0) {
+    if (use_bvh && scene_of(c)->num_nodes == 0) {
         set_error("mirt_trace_rays: use_bvh set but no tree uploaded");
         return MIRT_E_NOSCENE;
     }
@@ -2782,7 +2950,7 @@ int mirt_intersect_rays(mirt_ctx* c, const mirt_ray* rays, int n, int use_bvh, m
         set_error("mirt_intersect_rays: invalid arguments");
         return MIRT_E_INVALID;
     }
-    if (use_bvh && c->num_nodes == 0) {
+    if (use_bvh && scene_of(c)->num_nodes == 0) {
         set_error("mirt_intersect_rays: use_bvh set but no tree uploaded");
         return MIRT_E_NOSCENE;
     }
@@ -2824,7 +2992,7 @@ int mirt_any_hit_rays(mirt_ctx* c, const mirt_ray* rays, int n, int use_bvh, int
         set_error("mirt_any_hit_rays: invalid arguments");
         return MIRT_E_INVALID;
     }
-    if (use_bvh && c->num_nodes == 0) {
+    if (use_bvh && scene_of(c)->num_nodes == 0) {
         set_error("mirt_any_hit_rays: use_bvh set but no tree uploaded");
         return MIRT_E_NOSCENE;
     }
@@ -2881,17 +3049,18 @@ int mirt_bvh_overlay(mirt_ctx* c, const mirt_camera* cam, int width, int height,
     if (!rc) rc = ensure((void**)&c->d_out, &c->out_cap, 4 * pixels + 4);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_overlay, 0, 4 * pixels, c->stream));
-    const uint64_t lines = (uint64_t)c->num_nodes * 60;
+    const Scene* sn = scene_of(c);
+    const uint64_t lines = (uint64_t)sn->num_nodes * 60;
     if (lines > 0xffffffffull) {
         set_error("mirt_bvh_overlay: too many nodes");
         return MIRT_E_INVALID;
     }
     if (lines) {
-        overlay_lines_kernel<<<(unsigned)((lines + 255) / 256), 256, 0, c->stream>>>(o, c->d_nodes32, c->d_ndepth,
+        overlay_lines_kernel<<<(unsigned)((lines + 255) / 256), 256, 0, c->stream>>>(o, sn->d_nodes32, sn->d_ndepth,
                                                                                      (uint32_t)lines, c->d_overlay);
         HIP_TRY(hipGetLastError());
     }
-    overlay_colour_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, c->stream>>>(c->d_overlay, c->d_ndepth, pixels,
+    overlay_colour_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, c->stream>>>(c->d_overlay, sn->d_ndepth, pixels,
                                                                                  c->d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->d_out, 4 * pixels, hipMemcpyDeviceToHost, c->stream));

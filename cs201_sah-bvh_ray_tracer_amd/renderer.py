@@ -451,13 +451,34 @@ class Renderer:
 
     def update_scene(self, spheres, start=0, end=None, max_decay=0.0):
         """Refit the resident scene to `spheres` (a numpy abi.SPHERE array in
-        the scene's order) and rebuild it instead when the refit tree's cost
+        the scene's order, or a torch tensor on this context's device as for
+        refit_scene: then mirt_scene_update_device_ptr reads it in place, and
+        reordered (uint8, n x 20) and perm (int32) come back as tensors on
+        that device) and rebuild it instead when the refit tree's cost
         has grown past max_decay times the cost of the tree the last
         update_scene installed (mirt_scene_update_device; max_decay <= 0 never
         rebuilds). Returns (reordered, perm, result): the spheres in the order
         the scene now holds them, reordered[i] == spheres[perm[i]] (the
         identity unless rebuilt), and the mirt_update_result fields as a dict
         (rebuilt, on_device, base_cost, cost, decay, installed, total_ms)."""
+        if not isinstance(spheres, np.ndarray) and hasattr(spheres, "data_ptr"):
+            import torch
+            nbytes = spheres.numel() * spheres.element_size()
+            if not spheres.is_cuda or spheres.device.index != self.device or not spheres.is_contiguous() \
+                    or nbytes % abi.SPHERE.itemsize:
+                raise MirtError("update_scene: the tensor must be contiguous, on this context's device and hold "
+                                "20-byte spheres")
+            n = nbytes // abi.SPHERE.itemsize
+            end = n if end is None else end
+            reordered = torch.zeros((n, abi.SPHERE.itemsize), dtype=torch.uint8, device=spheres.device)
+            perm = torch.zeros(n, dtype=torch.int32, device=spheres.device)
+            res = abi.UpdateResult()
+            torch.cuda.current_stream(spheres.device).synchronize()  # the tensors' producers: another stream
+            check(self.L.mirt_scene_update_device_ptr(
+                self.h, C.c_void_p(spheres.data_ptr()) if n else None, n, start, end, max_decay,
+                C.c_void_p(reordered.data_ptr()) if n else None, C.c_void_p(perm.data_ptr()) if n else None,
+                C.byref(res)), "mirt_scene_update_device_ptr")
+            return reordered, perm, _fields(res)
         spheres = np.ascontiguousarray(spheres, abi.SPHERE)
         n = len(spheres)
         end = n if end is None else end
@@ -517,6 +538,18 @@ class Renderer:
         of one accumulating display loop with frames in flight; None: a
         private buffer again."""
         check(self.L.mirt_ctx_share_accum(self.h, owner.h if owner is not None else None), "mirt_ctx_share_accum")
+
+    def share_scene(self, owner):
+        """Render `owner`'s resident scene (mirt_ctx_share_scene): installs and
+        reads through either context then concern one scene, and frames in
+        flight finish on the scene they were enqueued on. None: a private slot
+        again, still holding the scene the group has now."""
+        check(self.L.mirt_ctx_share_scene(self.h, owner.h if owner is not None else None), "mirt_ctx_share_scene")
+
+    def scene_id(self):
+        """mirt_ctx_scene_id: the stamp of the resident scene (0: none); equal
+        across the contexts that share it, new with every install."""
+        return int(self.L.mirt_ctx_scene_id(self.h))
 
     def accum(self, count):
         out = np.zeros(count, np.float32)
@@ -719,6 +752,7 @@ class MultiRenderer:
         check(self.L.mirt_multi_create(devs, len(devices), lanes, flags, C.byref(h)), "mirt_multi_create")
         self.h = h
         self.devices = list(devices)
+        self.queue_ahead = bool(queue_ahead)
         self.lanes = self.L.mirt_multi_lanes(h)   # launch slots (2 x lanes with queue_ahead)
         self.launches = 0   # launch k runs on lane k % lanes (mirt_multi's rotation)
 
@@ -772,6 +806,59 @@ class MultiRenderer:
                                                       len(bvh.nodes)), "mirt_multi_scene_upload_flat")
         else:
             check(self.L.mirt_multi_scene_upload(self.h, ptr(spheres), len(spheres), bvh), "mirt_multi_scene_upload")
+
+    def build_scene(self, spheres, start=0, end=None, depth=0):
+        """Renderer.build_scene once per device (mirt_multi_scene_build_device):
+        the contexts of a device share the one scene. Launches in flight are
+        not waited for; they deliver the old scene's frames. Returns the
+        spheres as reordered."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        end = len(spheres) if end is None else end
+        out = np.zeros(len(spheres), abi.SPHERE)
+        check(self.L.mirt_multi_scene_build_device(self.h, ptr(spheres), len(spheres), start, end, depth, ptr(out)),
+              "mirt_multi_scene_build_device")
+        return out
+
+    def refit_scene(self, spheres, end=None):
+        """Renderer.refit_scene once per device (mirt_multi_scene_refit_device),
+        under launches in flight."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        n = len(spheres)
+        end = n if end is None else end
+        check(self.L.mirt_multi_scene_refit_device(self.h, ptr(spheres) if n else None, n, end),
+              "mirt_multi_scene_refit_device")
+
+    def update_scene(self, spheres, start=0, end=None, max_decay=0.0):
+        """Renderer.update_scene once per device (mirt_multi_scene_update_device),
+        under launches in flight; (reordered, perm, result) of the first
+        device."""
+        spheres = np.ascontiguousarray(spheres, abi.SPHERE)
+        n = len(spheres)
+        end = n if end is None else end
+        reordered = np.zeros(n, abi.SPHERE)
+        perm = np.zeros(n, np.int32)
+        res = abi.UpdateResult()
+        check(self.L.mirt_multi_scene_update_device(self.h, ptr(spheres) if n else None, n, start, end, max_decay,
+                                                    ptr(reordered) if n else None, ptr(perm) if n else None,
+                                                    C.byref(res)), "mirt_multi_scene_update_device")
+        return reordered, perm, _fields(res)
+
+    def scene_ids(self):
+        """The distinct mirt_ctx_scene_id values of the object's contexts: one
+        per device once they share, one per context after upload()."""
+        contexts = self.lanes // 2 if self.queue_ahead else self.lanes
+        return sorted({int(self.L.mirt_ctx_scene_id(self.ctx(l, r))) for l in range(contexts)
+                       for r in range(self.size)})
+
+    def resident_layout(self, lane, rank):
+        """Renderer.resident_layout of the scene (lane, rank)'s context renders."""
+        view = Renderer.__new__(Renderer)   # a view: the handle stays the object's
+        view.L, view.h = self.L, None
+        try:
+            view.h = self.ctx(lane, rank)
+            return view.resident_layout()
+        finally:
+            view.h = None
 
     def set_option(self, option, value):
         """MULTI_OPT_* (timeout, emulation) or a MIRT_OPT_* for every context."""

@@ -444,6 +444,15 @@ typedef struct mirt_update_result {
 } mirt_update_result;
 int mirt_scene_update_device(mirt_ctx *ctx, const mirt_sphere *spheres, int num_spheres, int start, int end,
                              double max_decay, mirt_sphere *reordered, int32_t *perm, mirt_update_result *out);
+/* The same with the spheres read from device memory on the ctx's stream (not
+   written), and `reordered` and `perm` (either may be NULL) written to device
+   memory: for a caller that animates on the GPU. The decision, the resident
+   arrays, the base cost rule and *out are mirt_scene_update_device's. On the
+   paths the kernels accept no sphere, colour or permutation crosses the host
+   link; declined inputs are fetched, take the host path and have reordered
+   and perm uploaded. d_reordered == d_spheres is MIRT_E_INVALID. Blocking. */
+int mirt_scene_update_device_ptr(mirt_ctx *ctx, const void *d_spheres, int num_spheres, int start, int end,
+                                 double max_decay, void *d_reordered, int32_t *d_perm, mirt_update_result *out);
 
 /* ---------------------------------------------------------- rendering */
 
@@ -518,6 +527,45 @@ int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
    buffer must be driven from ONE host thread (the call order is the fold
    order). */
 int mirt_ctx_share_accum(mirt_ctx *ctx, mirt_ctx *owner);
+
+/* A moving scene under frames in flight: several ctxs of one device render ONE
+   resident scene. A ctx renders the scene in its scene slot, by default a slot
+   of its own. After mirt_ctx_share_scene(ctx, owner), ctx uses owner's slot;
+   the two, and whoever else shares it, form a group. owner NULL or ctx itself:
+   ctx gets a private slot again, which still holds the scene the group had at
+   that moment -- the arrays stay shared, and read-only, until either slot's
+   next install. Both ctxs must be on the same device (else MIRT_E_INVALID); a
+   NULL ctx is MIRT_E_INVALID before any HIP call. Waits for ctx's own enqueued
+   frames first, as mirt_ctx_share_accum does.
+     Installs are group-wide: mirt_scene_upload, _upload_flat,
+       _upload_flat_device, mirt_scene_build_device,
+       mirt_scene_refit_device[_ptr] and mirt_scene_update_device[_ptr],
+       through any member, install the scene for every member.
+     Reads are group-wide: the refit's input tree, mirt_scene_quality,
+       mirt_scene_resident_layout, the overlay, the per-ray calls and the
+       frames read the group's scene through any member. The base cost of
+       mirt_scene_update_device belongs to the slot, not to the ctx.
+     Per ctx stay: the options, the statistics (mirt_last_*_stats), the build
+       scratch and the frame scratch.
+     Frames in flight: a frame enqueued on any member before an install
+       renders, to its last pixel, the scene that was resident when it was
+       enqueued. No array of a replaced scene is released or rewritten while a
+       frame enqueued on a member's stream can still read it: an install
+       records an event on the stream of every member that has work in
+       flight, and the replaced scene is freed once all have passed (looked
+       at by the slot's later installs, and waited for when the slot's last
+       member is destroyed).
+     Publication: all scene calls are blocking; the new arrays are complete
+       before any member can enqueue a frame on them.
+     Destroying a member releases its reference: the scene lives as long as
+       any member, or any frame in flight, holds it.
+   The members of a group must be driven from ONE host thread.
+   mirt_ctx_scene_id: a process-wide counter value stamped on a scene when it
+   is installed, 0 for "no scene" (and for a NULL ctx). The members of a group,
+   and a ctx that left with the scene, report the same id; every install gives
+   a new one. */
+int mirt_ctx_share_scene(mirt_ctx *ctx, mirt_ctx *owner);
+uint64_t mirt_ctx_scene_id(mirt_ctx *ctx);
 
 /* trace_ray (renderer.c:21-77) on n arbitrary rays; ray i uses RNG contract
    pixel index i. */

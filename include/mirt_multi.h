@@ -150,10 +150,47 @@ int mirt_multi_set_option(mirt_multi *m, int option, int value);
 int mirt_multi_get_option(mirt_multi *m, int option);
 
 /* mirt_scene_upload / mirt_scene_upload_flat to every context (the scene is
-   replicated on every device; call after the build reordered the spheres). */
+   replicated in every context; call after the build reordered the spheres).
+   Waits for all lanes; every context has a private scene afterwards. */
 int mirt_multi_scene_upload(mirt_multi *m, const mirt_sphere *spheres, int num_spheres, const mirt_bvh_node *root);
 int mirt_multi_scene_upload_flat(mirt_multi *m, const mirt_sphere *spheres, int num_spheres, const mirt_node *nodes,
                                  int num_nodes);
+
+/* A scene that moves under launches in flight: mirt_scene_build_device,
+   mirt_scene_refit_device and mirt_scene_update_device of mirt.h, run once per
+   distinct device of the object. All contexts the object owns on one device
+   (every lane's context of every rank placed there; with
+   MIRT_MULTI_QUEUE_AHEAD the owning lanes') join the scene slot
+   (mirt_ctx_share_scene) of that device's first context -- lowest lane, then
+   lowest rank -- so a device holds ONE scene however many ranks and lanes it
+   serves, and the call runs on that leader. The contract, the declined inputs
+   (host path, on_device = 0) and the results are the single-context call's,
+   byte for byte, on every device; `reordered`, `perm` and `out` are filled from
+   the first device's leader. The builds are bit-identical across devices, so
+   every device reaches the same `rebuilt`; a mismatch fails the object
+   (MIRT_E_DEVICE).
+   Ordering: the calls do NOT wait for launches to finish. They wait until the
+   rank threads have issued every launch already handed to them (bounded by
+   MIRT_MULTI_OPT_TIMEOUT_MS). Launches enqueued before the call deliver
+   frames of the old scene, launches enqueued after it frames of the new one.
+   (The leader's kernels run on its own stream, behind the launch its lane has
+   in flight; the first such call on an object whose contexts do not share yet
+   -- after create, or after mirt_multi_scene_upload[_flat], which leave every
+   context with a private scene -- waits for all lanes once, then the contexts
+   of each device take their leader's scene and drop their own identical one.)
+   Errors: arguments, a failed object, MIRT_E_NOSCENE (refit and update without
+   a scene) and a wrong num_spheres are reported before anything is changed. A
+   failure on a later device after an earlier one has installed leaves the
+   devices disagreeing: the object fails, as after a timeout. The devices run
+   one after the other from the caller's thread.
+   Verification status: one device only (any number of same-device ranks and
+   lanes); the loop over distinct devices has not run on a multi-GPU node. */
+int mirt_multi_scene_build_device(mirt_multi *m, const mirt_sphere *spheres, int num_spheres,
+                                  int start, int end, int depth, mirt_sphere *reordered);
+int mirt_multi_scene_refit_device(mirt_multi *m, const mirt_sphere *spheres, int num_spheres, int end);
+int mirt_multi_scene_update_device(mirt_multi *m, const mirt_sphere *spheres, int num_spheres,
+                                   int start, int end, double max_decay,
+                                   mirt_sphere *reordered, int32_t *perm, mirt_update_result *out);
 
 /* One launch of `nframes` successive frames (RNG samples fd->sample ..
    fd->sample + nframes - 1; accumulating: divisors fd->frames + j, as nframes
