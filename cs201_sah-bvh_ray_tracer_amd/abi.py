@@ -96,6 +96,11 @@ class FrameDesc(C.Structure):
                 ("jitter", C.c_int32), ("lead_skip", C.c_int32)]
 
 
+class PrimaryPlanes(C.Structure):
+    """mirt_primary_planes (a NULL member is not written)"""
+    _fields_ = [("t", C.c_void_p), ("sphere", C.c_void_p), ("normal", C.c_void_p)]
+
+
 class Counts(C.Structure):
     """mirt_counts"""
     _fields_ = [("rays", C.c_uint64), ("nodes", C.c_uint64), ("spheres", C.c_uint64), ("hits", C.c_uint64),
@@ -216,6 +221,9 @@ SIGNATURES = [
     ("mirt_render_frame", I, [P, P, P, P]),
     ("mirt_render_frame_device", I, [P, P, P, P, P, P]),
     ("mirt_render_frame_async", I, [P, P, P, P]),
+    ("mirt_render_frame_planes", I, [P, P, P, P, P]),
+    ("mirt_render_frame_planes_device", I, [P, P, P, P, P, P, P]),
+    ("mirt_render_frame_planes_async", I, [P, P, P, P, P]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),

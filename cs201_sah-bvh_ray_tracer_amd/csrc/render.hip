@@ -143,18 +143,20 @@ struct Deferred {
 
 // One pixel of the pixel loop: main.c:362-366 ray, trace_ray, then the
 // display/accumulation of main.c:368-372 (fresh) or main.c:394-405.
-template <bool FAST, bool COUNT>
+// PLANES = Planes (a frame with planes, else no such argument): the camera
+// ray's closest hit also goes to the pixel's element of `planes`.
+template <bool FAST, bool COUNT, class... PLANES>
 __device__ __forceinline__ void render_pixel(const DevScene& sc, const FrameConst& f, int x, int r, bool alive,
                                              bool skip_generic, uint32_t* __restrict__ out, float* __restrict__ acc,
                                              Counters& cnt, uint32_t* cstack, int cstride,
-                                             uint32_t* wstk = nullptr)
+                                             uint32_t* wstk = nullptr, PLANES... planes)
 {
     const int y = alive ? shard_row_to_y(f, r) : 0;
     const Ray ray = camera_ray(f, alive ? x : 0, y, row_sample(f, r));
     if (skip_generic && alive && slab_ray(ray).generic) alive = false;  // a deferred wave traces it
     const uint64_t key = pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r));
     const uint32_t c = trace_path<FAST, COUNT>(sc, ray, alive, f.depth, f.use_bvh != 0, key, cnt, cstack,
-                                                     cstride, wstk);
+                                                     cstride, wstk, PlaneSlot{planes, (size_t)r * f.width + x}...);
     if (!alive) return;
     const size_t i = (size_t)r * f.width + x;
     uint32_t shown = c;
@@ -176,10 +178,15 @@ __device__ __forceinline__ void render_pixel(const DevScene& sc, const FrameCons
 }
 
 // The pixel loop of main.c:358-374 (fresh) / main.c:382-407 (accumulate).
-template <bool FAST, bool COUNT>
+// PLANES: no argument at all, or the Planes of a frame with planes
+// (mirt_render_frame_planes) -- an instantiation of its own, so that the
+// kernel of a frame without planes keeps its arguments and its code. With
+// planes each pixel's lane -- the deferred wave's lane 0 for a deferred pixel
+// -- also stores the hit trace_path finds at level 0.
+template <bool FAST, bool COUNT, class... PLANES>
 __global__ __launch_bounds__(512) void render_kernel(DevScene sc, FrameConst f, uint32_t* __restrict__ out,
                                                       float* __restrict__ acc, mirt_counts* counts,
-                                                      uint32_t* wave_stats, Deferred dfr)
+                                                      uint32_t* wave_stats, Deferred dfr, PLANES... planes)
 {
     uint64_t t0 = 0;
     if (COUNT) t0 = __builtin_amdgcn_s_memrealtime();
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(512) void render_kernel(DevScene sc, FrameConst f, 
         for (uint32_t j = blockIdx.x * bw + wave; j < n; j += stride) {
             const uint32_t p = __builtin_amdgcn_readfirstlane(dfr.list[j]);
             render_pixel<FAST, COUNT>(sc, f, (int)(p % f.width), (int)(p / f.width), (threadIdx.x & 63) == 0,
-                                            false, out, acc, cnt, cstack + threadIdx.x, blockDim.x, wstk);
+                                            false, out, acc, cnt, cstack + threadIdx.x, blockDim.x, wstk, planes...);
         }
         if (COUNT) add_counts(counts, cnt);
         return;
@@ -207,7 +214,7 @@ __global__ __launch_bounds__(512) void render_kernel(DevScene sc, FrameConst f, 
     const int x = (tile % tiles_x) * 8 + (lane & 7);
     const int r = (tile / tiles_x) * 8 + (lane >> 3);
     render_pixel<FAST, COUNT>(sc, f, x, r, x < f.width && r < f.num_rows, dfr.blocks > 0, out, acc, cnt,
-                                    cstack + threadIdx.x, blockDim.x, wstk);
+                                    cstack + threadIdx.x, blockDim.x, wstk, planes...);
     if (COUNT) {
         add_counts(counts, cnt);
         if (wave_stats && lane == 0) {
@@ -349,9 +356,12 @@ struct BounceRec {
 // other walk, so it keeps the register budget of the packet walk alone.
 // BND (ORD only): the camera is within 4C of the origin (DevScene::o_bound):
 // the packet walk tests the grown inner-child boxes without margins (trace.h).
-template <bool FAST, bool ORD, bool BND = false>
-// Register budget of the ordered camera-packet kernel (ORD): 8 waves per SIMD (64 VGPRs, no
-// scratch; 67 and 7 waves without the attribute). With four frames in flight
+// PLANES (as for render_kernel): with planes, the lane that owns a pixel
+// stores its closest hit where the walk returns it; a pixel handed to a
+// deferred wave is stored by that wave's lane 0 (render_pixel).
+template <bool FAST, bool ORD, bool BND = false, class... PLANES>
+// Register budget of the ordered camera-packet kernel (ORD): 8 waves per SIMD (64 VGPRs;
+// 67 and 7 waves without the attribute). With four frames in flight
 // its waves share the CUs with the bounce passes, and the eighth wave hides
 // more of the packet walk's scalar-load latency (1080p/10k +0.3-1.1%,
 // 1080p/100k +3.7%, profiles/r02_ab/r02ax_primary_waves8_*).
@@ -368,7 +378,7 @@ template <bool FAST, bool ORD, bool BND = false>
 __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene sc, FrameConst f, uint32_t* __restrict__ out,
                                                       float* __restrict__ acc, Deferred dfr,
                                                       BounceRec* __restrict__ queue, uint32_t* __restrict__ qctl,
-                                                      int octants = 1)
+                                                      int octants = 1, PLANES... planes)
 {
     __shared__ uint32_t cstack[ORD ? 1 : kMaxDepth * 256];
     Counters cnt{0, 0, 0, 0, 0};
@@ -388,7 +398,7 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
         for (uint32_t j = blockIdx.x * 4 + wave; j < n; j += stride) {
             const uint32_t p = __builtin_amdgcn_readfirstlane(dfr.list[j]);
             render_pixel<FAST, false>(sc, f, (int)(p % f.width), (int)(p / f.width), lane == 0, false,
-                                                     out, acc, cnt, cstack + threadIdx.x, 256);
+                                                     out, acc, cnt, cstack + threadIdx.x, 256, nullptr, planes...);
         }
         return;
     }
@@ -424,6 +434,9 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
     } else
         closest_hit<true, FAST, false>(sc, ray, alive, t, s, cnt);
     const size_t i = (size_t)r * f.width + x;
+    if constexpr (sizeof...(PLANES) > 0) {
+        if (alive) (store_planes(planes, i, sc, ray, t, s), ...);
+    }
     bool push = false;
     BounceRec rec;
     if (alive) {
@@ -1615,6 +1628,9 @@ struct mirt_ctx {
     void* d_queue = nullptr;    // wavefront: {count, head} + bounce records
     size_t queue_cap = 0;
     bool lone_frame = false;    // mirt_render_frame's frame: the first bounces queued in tile order
+    Planes planes;              // mirt_render_frame_planes*: the planes of the frame being enqueued
+    void* d_planes = nullptr;   // planes of the blocking / async forms, copied to the host behind the frame
+    size_t planes_cap = 0;
     int queue_order = 0;        // MIRT_OPT_QUEUE_ORDER: 0 auto (tile order for lone_frame), 1 octants, 2 tile order
     uint32_t* d_defer = nullptr;  // [count, list...]
     size_t defer_cap = 0;
@@ -1895,11 +1911,28 @@ bool ctx_ok(mirt_ctx* c, bool need_scene, const char* fn)
     return hipSetDevice(c->device) == hipSuccess;
 }
 
+bool has_planes(const Planes& pl) { return pl.t || pl.sphere || pl.normal; }
+
+// The camera-packet kernel of a frame, with the planes' stores if it has any.
+template <bool FAST, bool ORD, bool BND>
+void launch_primary(int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f, uint32_t* d_out, float* d_acc,
+                    Deferred dfr, BounceRec* queue, uint32_t* qctl, int octants, const Planes& pl)
+{
+    if (has_planes(pl))
+        primary_kernel<FAST, ORD, BND><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants, pl);
+    else
+        primary_kernel<FAST, ORD, BND><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants);
+}
+
 template <bool COUNT>
 void dispatch_render(bool fast, const DevScene& sc, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s,
-                     int blocks, int bw, mirt_counts* d_counts, uint32_t* d_ws, Deferred dfr)
+                     int blocks, int bw, mirt_counts* d_counts, uint32_t* d_ws, Deferred dfr, const Planes& pl)
 {
-    if (fast)
+    if (!COUNT && has_planes(pl) && fast)
+        render_kernel<true, false><<<blocks + dfr.blocks, 64 * bw, 0, s>>>(sc, f, d_out, d_acc, nullptr, nullptr, dfr, pl);
+    else if (!COUNT && has_planes(pl))
+        render_kernel<false, false><<<blocks + dfr.blocks, 64 * bw, 0, s>>>(sc, f, d_out, d_acc, nullptr, nullptr, dfr, pl);
+    else if (fast)
         render_kernel<true, COUNT><<<blocks + dfr.blocks, 64 * bw, 0, s>>>(sc, f, d_out, d_acc, d_counts, d_ws, dfr);
     else
         render_kernel<false, COUNT><<<blocks + dfr.blocks, 64 * bw, 0, s>>>(sc, f, d_out, d_acc, d_counts, d_ws, dfr);
@@ -2033,9 +2066,9 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const int ptiles = f.samples >= 4 ? ((f.width + 3) / 4) * ((f.shard_rows + 3) / 4) * ((f.samples + 3) / 4)
                                           : tiles;
         if (camera_bounded(c, f))
-            primary_kernel<true, true, true><<<(ptiles + 3) / 4, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl);
+            launch_primary<true, true, true>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes);
         else
-            primary_kernel<true, true><<<(ptiles + 3) / 4, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl);
+            launch_primary<true, true, false>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes);
         HIP_TRY(hipGetLastError());
         if (int rc2 = fold()) return rc2;
         if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
@@ -2056,15 +2089,15 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const int pblocks = (ptiles + 3) / 4 + dfr.blocks;
         const int bblocks = c->bounce_blocks_opt ? c->bounce_blocks_opt : c->bounce_blocks;
         const size_t blds = bounce_lds_bytes(f.depth);
+        const int oq = octant_queue(c);
         if (c->fast_slab && sc.ordered && camera_bounded(c, f))
-            primary_kernel<true, true, true><<<pblocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl,
-                                                                     octant_queue(c));
+            launch_primary<true, true, true>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
         else if (c->fast_slab && sc.ordered)
-            primary_kernel<true, true><<<pblocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octant_queue(c));
+            launch_primary<true, true, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
         else if (c->fast_slab)
-            primary_kernel<true, false><<<pblocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octant_queue(c));
+            launch_primary<true, false, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
         else
-            primary_kernel<false, false><<<pblocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octant_queue(c));
+            launch_primary<false, false, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ph1[ps], s));
         if (d_bdiag && sc.wide)
@@ -2086,9 +2119,9 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         return MIRT_OK;
     }
     if (d_counts)
-        dispatch_render<true>(true, sc, f, d_out, d_acc, s, blocks, bw, d_counts, d_wave_stats, dfr);
+        dispatch_render<true>(true, sc, f, d_out, d_acc, s, blocks, bw, d_counts, d_wave_stats, dfr, c->planes);
     else
-        dispatch_render<false>(c->fast_slab != 0, sc, f, d_out, d_acc, s, blocks, bw, nullptr, nullptr, dfr);
+        dispatch_render<false>(c->fast_slab != 0, sc, f, d_out, d_acc, s, blocks, bw, nullptr, nullptr, dfr, c->planes);
     HIP_TRY(hipGetLastError());
     if (int rc = fold()) return rc;
     if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
@@ -2204,7 +2237,7 @@ void mirt_destroy(mirt_ctx* c)
     mirt::build_state_free(c->build);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
-                    (void*)c->d_keys, (void*)c->d_overlay})
+                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes})
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2623,7 +2656,23 @@ bool host_page_locked(const void* p, size_t bytes)
 }  // namespace mirt
 }
 
-static int render_frame_blocking(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out);
+// The frame and the delivery of its display to `out`, enqueued on the ctx's
+// stream. in_place and a page-locked destination (the recipe for main.c's
+// reused frame buffer: mirt_host_register): the frame kernels store each
+// pixel straight into it, so the frame is in host memory when they end -- no
+// copy after them (one frame, the ctx's own accumulation: nothing reads the
+// output back)
+static int enqueue_frame_to_host(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out,
+                                 bool in_place, const char* fn)
+{
+    if (c && in_place && out && frame_desc_valid(fd) && fd->samples <= 1 && !accum_chain(c)) {
+        if (uint32_t* d = host_mapped(out, (size_t)shard_row_count(fd) * fd->width * 4)) {
+            uint32_t* disp = nullptr;
+            return enqueue_frame(c, cam, fd, d, &disp, fn);
+        }
+    }
+    return enqueue_host_frame(c, cam, fd, out, fn);
+}
 
 // The blocking call renders one frame with nothing after it on the ctx: its
 // first bounces go to the queue in tile order (lone_frame), which the
@@ -2631,27 +2680,9 @@ static int render_frame_blocking(mirt_ctx* c, const mirt_camera* cam, const mirt
 int mirt_render_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out)
 {
     if (c) c->lone_frame = true;
-    const int rc = render_frame_blocking(c, cam, fd, out);
+    const int rc = enqueue_frame_to_host(c, cam, fd, out, c && c->zero_copy, "mirt_render_frame");
     if (c) c->lone_frame = false;
-    return rc;
-}
-
-static int render_frame_blocking(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out)
-{
-    // a page-locked destination (the recipe for main.c's reused frame buffer:
-    // mirt_host_register): the frame kernels store each pixel straight into
-    // it, so the frame is in host memory when they end -- no copy after them
-    // (one frame, the ctx's own accumulation: nothing reads the output back)
-    if (c && c->zero_copy && out && frame_desc_valid(fd) && fd->samples <= 1 && !accum_chain(c)) {
-        if (uint32_t* d = host_mapped(out, (size_t)shard_row_count(fd) * fd->width * 4)) {
-            uint32_t* disp = nullptr;
-            if (int rc = enqueue_frame(c, cam, fd, d, &disp, "mirt_render_frame")) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-            return MIRT_OK;
-        }
-    }
-    if (int rc = enqueue_host_frame(c, cam, fd, out, "mirt_render_frame")) return rc;
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
@@ -2661,13 +2692,85 @@ int mirt_render_frame_async(mirt_ctx* c, const mirt_camera* cam, const mirt_fram
 {
     // MIRT_OPT_ZERO_COPY 2: frames in flight into page-locked memory are
     // written in place too (no DMA behind each frame's kernels)
-    if (c && c->zero_copy == 2 && out && frame_desc_valid(fd) && fd->samples <= 1 && !accum_chain(c)) {
-        if (uint32_t* d = host_mapped(out, (size_t)shard_row_count(fd) * fd->width * 4)) {
-            uint32_t* disp = nullptr;
-            return enqueue_frame(c, cam, fd, d, &disp, "mirt_render_frame_async");
-        }
+    return enqueue_frame_to_host(c, cam, fd, out, c && c->zero_copy == 2, "mirt_render_frame_async");
+}
+
+// ---- frames with planes (mirt_primary_planes)
+
+// What the planes forms check on top of their plain siblings, before the ctx
+// is used and before any HIP call.
+static bool planes_args_ok(const mirt_ctx* c, const mirt_frame_desc* fd, const mirt_primary_planes* pl, const char* fn)
+{
+    if (!c) {
+        set_error("%s: null context", fn);
+        return false;
     }
-    return enqueue_host_frame(c, cam, fd, out, "mirt_render_frame_async");
+    if (!pl || !(pl->t || pl->sphere || pl->normal) || (fd && fd->max_depth < 1)) {
+        set_error("%s: invalid arguments", fn);
+        return false;
+    }
+    return true;
+}
+
+int mirt_render_frame_planes_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
+                                    float* d_acc, const mirt_primary_planes* d_planes, void* stream)
+{
+    if (!planes_args_ok(c, fd, d_planes, "mirt_render_frame_planes_device")) return MIRT_E_INVALID;
+    c->planes = Planes{d_planes->t, d_planes->sphere, d_planes->normal};
+    const int rc = mirt_render_frame_device(c, cam, fd, d_out, d_acc, stream);
+    c->planes = Planes{};
+    return rc;
+}
+
+// The blocking and async forms: the frame stores its planes into device
+// memory the ctx keeps (grown by `ensure`, never freed per frame), the
+// members the caller asked for one after another, and they are copied to the
+// caller's host pointers behind the frame on the ctx's stream.
+static int render_frame_planes_host(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out,
+                                    const mirt_primary_planes* pl, bool blocking, const char* fn)
+{
+    if (!planes_args_ok(c, fd, pl, fn)) return MIRT_E_INVALID;
+    if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
+    if (!cam || !frame_desc_valid(fd) || !out) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    const size_t n = (size_t)shard_row_count(fd) * fd->width * (fd->samples > 1 ? fd->samples : 1);
+    const size_t off_s = pl->t ? 4 * n : 0, off_n = off_s + (pl->sphere ? 4 * n : 0);
+    const size_t bytes = off_n + (pl->normal ? 12 * n : 0);
+    // the buffer grows: an earlier frame's copies out of it have ended first
+    if (bytes > c->planes_cap) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = ensure(&c->d_planes, &c->planes_cap, bytes)) return rc;
+    char* const d = (char*)c->d_planes;
+    c->planes = Planes{pl->t ? (float*)d : nullptr, pl->sphere ? (int32_t*)(d + off_s) : nullptr,
+                       pl->normal ? (float*)(d + off_n) : nullptr};
+    const Planes dev = c->planes;
+    c->lone_frame = blocking;
+    const int rc = enqueue_frame_to_host(c, cam, fd, out, blocking ? c->zero_copy != 0 : c->zero_copy == 2, fn);
+    c->lone_frame = false;
+    c->planes = Planes{};
+    if (rc) return rc;
+    if (n) {
+        if (pl->t) HIP_TRY(hipMemcpyAsync(pl->t, dev.t, 4 * n, hipMemcpyDeviceToHost, c->stream));
+        if (pl->sphere) HIP_TRY(hipMemcpyAsync(pl->sphere, dev.sphere, 4 * n, hipMemcpyDeviceToHost, c->stream));
+        if (pl->normal) HIP_TRY(hipMemcpyAsync(pl->normal, dev.normal, 12 * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!blocking) return MIRT_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    return MIRT_OK;
+}
+
+int mirt_render_frame_planes(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out,
+                             const mirt_primary_planes* planes)
+{
+    return render_frame_planes_host(c, cam, fd, out, planes, true, "mirt_render_frame_planes");
+}
+
+int mirt_render_frame_planes_async(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out,
+                                   const mirt_primary_planes* planes)
+{
+    return render_frame_planes_host(c, cam, fd, out, planes, false, "mirt_render_frame_planes_async");
 }
 
 int mirt_ctx_wait(mirt_ctx* c)

@@ -1644,6 +1644,36 @@ __device__ __forceinline__ void hit_point_normal(const Ray& r, float t, float4 s
     normalize3(n[0], n[1], n[2]);
 }
 
+// The primary-hit planes of a frame (mirt.h mirt_primary_planes), device
+// pointers indexed like the colour output; a null plane is not written.
+struct Planes {
+    float* t = nullptr;
+    int32_t* sphere = nullptr;
+    float* normal = nullptr;
+};
+
+// One pixel's element of the planes.
+struct PlaneSlot {
+    Planes pl;
+    size_t i;
+};
+
+// Element i of the planes from a camera ray's closest hit (t, s) as the walk
+// left it: what store_hit (mirt_intersect_rays) records for that ray.
+__device__ __forceinline__ void store_planes(const Planes& pl, size_t i, const DevScene& sc, const Ray& ray, float t,
+                                             int s)
+{
+    float p[3], n[3] = {0.0f, 0.0f, 0.0f};
+    if (s >= 0 && pl.normal) hit_point_normal(ray, t, sc.geo[s], p, n);
+    if (pl.t) pl.t[i] = s >= 0 ? t : 0.0f;
+    if (pl.sphere) pl.sphere[i] = s >= 0 ? s : -1;
+    if (pl.normal) {
+        pl.normal[3 * i] = n[0];
+        pl.normal[3 * i + 1] = n[1];
+        pl.normal[3 * i + 2] = n[2];
+    }
+}
+
 // sphere.c:19-32 with vec3.c:64-69 on the per-pixel stream: rejection-sample
 // p in the unit ball (x, y, z drawn in that order), normalise, flip into the
 // hemisphere of n.
@@ -1804,10 +1834,14 @@ enum Trav { kTravTile = 0, kTravWavefront = 5 };
 // The base colours of the hit levels (folded innermost-first at the end,
 // renderer.c:55-58) live in LDS, `cstack[level * cstride]`, one column per
 // thread, to keep them out of the register budget.
-template <bool FAST, bool COUNT>
+//
+// SLOT = PlaneSlot (mirt_render_frame_planes, else no such argument): the
+// camera ray's closest hit, known at level 0, also goes to that element of
+// the planes.
+template <bool FAST, bool COUNT, class... SLOT>
 __device__ __forceinline__ uint32_t trace_path(const DevScene& sc, Ray ray, bool alive, int depth, bool use_bvh,
                                                uint64_t key, Counters& cnt, uint32_t* cstack, int cstride,
-                                               uint32_t* wstk = nullptr)
+                                               uint32_t* wstk = nullptr, SLOT... slot)
 {
     int levels = 0;
     uint32_t tail = 255u << 24;  // renderer.c:23-24 depth exhausted -> (0,0,0,255)
@@ -1825,6 +1859,9 @@ __device__ __forceinline__ uint32_t trace_path(const DevScene& sc, Ray ray, bool
                 closest_hit<false, FAST, COUNT>(sc, ray, alive, t, s, cnt, wstk);
         } else {
             closest_brute<FAST, COUNT>(sc, ray, alive, t, s, cnt);
+        }
+        if constexpr (sizeof...(SLOT) > 0) {
+            if (alive && level == 0) (store_planes(slot.pl, slot.i, sc, ray, t, s), ...);
         }
         if (alive) {
             if (COUNT) cnt.rays++;

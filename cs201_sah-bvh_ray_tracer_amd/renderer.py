@@ -533,6 +533,66 @@ class Renderer:
                                               C.c_void_p(d_acc) if d_acc else None,
                                               C.c_void_p(stream or 0)), "mirt_render_frame_device")
 
+    # ---- frames with primary-hit planes (mirt_primary_planes)
+    PLANES = {"t": (np.float32, ()), "sphere": (np.int32, ()), "normal": (np.float32, (3,))}
+
+    @classmethod
+    def _planes_struct(cls, ptrs, fn):
+        """abi.PrimaryPlanes from {name: integer pointer}; unknown names are refused."""
+        bad = [k for k in ptrs if k not in cls.PLANES]
+        if bad:
+            raise MirtError(f"{fn}: no such plane {bad[0]!r} (have {', '.join(cls.PLANES)})")
+        return abi.PrimaryPlanes(**{k: int(v) for k, v in ptrs.items() if v})
+
+    def render_frame_planes(self, cam, width, height, planes=("t", "sphere", "normal"), **frame_desc_args):
+        """render_frame (frame_desc's keyword arguments) that also returns each
+        pixel's primary hit, stored by the frame's own camera walk: (rgba, dict)
+        with the asked-for planes "t" (float32; 0 on a miss), "sphere" (int32
+        index into the resident spheres; -1 on a miss) and "normal" (float32 x 3;
+        0 on a miss), each (rows, width[, 3]) in the shard's row order -- with
+        samples > 1 (samples, rows, width[, 3]), frame j's own hits in slab j,
+        while rgba is the display after the last frame."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        out = np.zeros((n, width, 4), np.uint8)
+        lead = (fd.samples, n, width) if fd.samples > 1 else (n, width)
+        self._planes_struct(dict.fromkeys(planes, 0), "render_frame_planes")   # the names
+        bufs = {k: np.zeros(lead + self.PLANES[k][1], self.PLANES[k][0]) for k in planes}
+        pl = self._planes_struct({k: b.ctypes.data for k, b in bufs.items()}, "render_frame_planes")
+        check(self.L.mirt_render_frame_planes(self.h, C.byref(cam), C.byref(fd), ptr(out), C.byref(pl)),
+              "mirt_render_frame_planes")
+        return out, bufs
+
+    def render_frame_planes_device(self, cam, fd, d_out, d_planes, d_acc=None, stream=None):
+        """render_frame_device that also stores the planes: d_planes maps "t" /
+        "sphere" / "normal" to integer device pointers (samples * rows * width
+        elements each, three floats per element for "normal")."""
+        pl = self._planes_struct(d_planes, "render_frame_planes_device")
+        check(self.L.mirt_render_frame_planes_device(self.h, C.byref(cam), C.byref(fd), C.c_void_p(d_out),
+                                                     C.c_void_p(d_acc) if d_acc else None, C.byref(pl),
+                                                     C.c_void_p(stream or 0)), "mirt_render_frame_planes_device")
+
+    def render_frame_planes_async(self, cam, fd, out, planes):
+        """render_frame_async that also copies the planes, behind the frame on
+        the ctx's stream: `planes` maps "t" / "sphere" / "normal" to HostBuffers
+        or C-contiguous arrays of samples * rows * width elements (float32,
+        int32, float32 x 3); all are complete after wait()."""
+        arr = out.array if isinstance(out, HostBuffer) else out
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        if arr.nbytes < n * fd.width * 4 or not arr.flags["C_CONTIGUOUS"]:
+            raise MirtError(f"render_frame_planes_async: output holds {arr.nbytes} bytes, the shard needs "
+                            f"{n * fd.width * 4}")
+        ptrs = {}
+        for k, buf in planes.items():
+            a = buf.array if isinstance(buf, HostBuffer) else buf
+            need = max(fd.samples, 1) * n * fd.width * (12 if k == "normal" else 4)
+            if a.nbytes < need or not a.flags["C_CONTIGUOUS"]:
+                raise MirtError(f"render_frame_planes_async: plane {k!r} holds {a.nbytes} bytes, the frame needs {need}")
+            ptrs[k] = a.ctypes.data
+        pl = self._planes_struct(ptrs, "render_frame_planes_async")
+        check(self.L.mirt_render_frame_planes_async(self.h, C.byref(cam), C.byref(fd), ptr(arr), C.byref(pl)),
+              "mirt_render_frame_planes_async")
+
     def share_accum(self, owner):
         """Use `owner`'s accumulation buffer (mirt_ctx_share_accum): the ctxs
         of one accumulating display loop with frames in flight; None: a

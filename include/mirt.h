@@ -512,6 +512,39 @@ void mirt_host_free(void *p);
 int mirt_host_register(void *p, size_t bytes);
 int mirt_host_unregister(void *p);
 
+/* A frame that also returns each pixel's primary hit: the closest hit of the
+   camera ray the frame traces for that pixel (with fd's jitter, sample and
+   shard), found by the walk the frame uses (fd->use_bvh: ray_bvh_intersect on
+   the resident tree, else the brute-force loop). Each plane is indexed exactly
+   as the colour output of the device form: `samples` slabs of num_rows * width,
+   pixel r * width + x in shard row order; slab j holds frame j's own hit (planes
+   are never accumulated). Element i is, byte for byte, the t, sphere and normal
+   of mirt_intersect_rays(mirt_camera_rays(fd))[i]. Sphere indices refer to the
+   scene that was resident when the frame was enqueued (mirt_ctx_scene_id; the
+   group's scene for members of a scene group). */
+typedef struct mirt_primary_planes {
+    float   *t;       /* HitRecord.t (hit.c:19-39) of the camera ray's closest hit; 0 on a miss      */
+    int32_t *sphere;  /* index into the resident (reordered) spheres; -1 on a miss                    */
+    float   *normal;  /* 3 floats per pixel, hit.c:32-33's normal; 0,0,0 on a miss                    */
+} mirt_primary_planes; /* a NULL member is not written; at least one must be non-NULL */
+
+/* mirt_render_frame / _device / _async with planes: the same arguments, checks
+   and errors, the same colours and accumulation buffer byte for byte, and in
+   addition MIRT_E_INVALID (before any device call) for a NULL ctx, NULL planes,
+   planes without a member, or fd->max_depth < 1. The hit is stored by the
+   frame's own camera walk, not by a second one. The blocking and async forms
+   take host pointers (samples * num_rows * width elements each; `out` still
+   receives the last display only) and copy the planes behind the frame on the
+   ctx's stream from device memory the ctx keeps; the device form takes device
+   pointers. */
+int mirt_render_frame_planes(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd, mirt_rgba8 *out,
+                             const mirt_primary_planes *planes);
+int mirt_render_frame_planes_device(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd,
+                                    uint32_t *d_out, float *d_accum, const mirt_primary_planes *d_planes,
+                                    void *stream);
+int mirt_render_frame_planes_async(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd, mirt_rgba8 *out,
+                                   const mirt_primary_planes *planes);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
