@@ -244,6 +244,8 @@ SIGNATURES = [
     ("mirt_hemisphere_probe", I, [P, P, P, P, P, I, P, P]),
     ("mirt_coop_geometry", I, [I, C.c_uint64, P, P, P, P]),
     ("mirt_pixel_rows", I, [I, I, I, I, I, I, P, C.c_int64, P]),
+    ("mirt_exact_t_pairs", I, [C.c_int64, P, P, P, P, P, P, P, P]),
+    ("mirt_sqrt_form_sweep", I, [P, P, P]),
     ("mirt_box_form_pairs", I, [P, P, P, P, I, I, P]),
     ("mirt_sphere_form_pairs", I, [P, P, P, P, I, I, P]),
     ("mirt_camera_rays", I, [P, P, P, P]),

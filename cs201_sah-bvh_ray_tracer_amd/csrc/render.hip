@@ -1359,8 +1359,12 @@ __global__ void box_form_pairs_kernel(DevScene sc, const mirt_ray* __restrict__ 
     out[i] = pass ? 1 : 0;
 }
 
-// sphere_t<FAST> on pairs (mirt_sphere_form_pairs): the returned float's bits
-template <bool FAST>
+// sphere_t on pairs (mirt_sphere_form_pairs): the returned float's bits.
+// MODE 0: the exact form; 1: the filtered form of the walks; 2: the filtered
+// form with the float-pair certification off (every pair the filter leaves
+// takes the f64 branch, which the walks reach once in some thousands of hits);
+// 3: not t but whether MODE 1 ran the f64 branch for the pair.
+template <int MODE>
 __global__ void sphere_form_pairs_kernel(const mirt_ray* __restrict__ rays, const mirt_sphere* __restrict__ sph,
                                          const float* __restrict__ best, int n, uint32_t* __restrict__ out)
 {
@@ -1369,7 +1373,33 @@ __global__ void sphere_form_pairs_kernel(const mirt_ray* __restrict__ rays, cons
     const mirt_ray rr = rays[i];
     const Ray ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
     const float4 g = make_float4(sph[i].center.x, sph[i].center.y, sph[i].center.z, sph[i].radius);
-    out[i] = __float_as_uint(sphere_t<FAST>(sph_ray(ray), g, best[i]));
+    if constexpr (MODE == 3) {
+        bool f64 = false;
+        (void)sphere_t<true>(sph_ray(ray), g, best[i], &f64);
+        out[i] = f64 ? 1u : 0u;
+    } else {
+        out[i] = __float_as_uint(sphere_t<MODE != 0, MODE != 2>(sph_ray(ray), g, best[i]));
+    }
+}
+
+// normalize3's binary32 root (sqrt_rn32) against vec3.c:22's binary64 form on
+// every non-negative finite float (mirt_sqrt_form_sweep): res[0] = mismatches,
+// res[1] = the least mismatching bit pattern (~0: none).
+__global__ void sqrt_form_sweep_kernel(unsigned long long* __restrict__ res)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    uint32_t bad = 0, first = ~0u;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < 0x7f800000ull; i += stride) {
+        const float x = __uint_as_float((uint32_t)i);
+        if (__float_as_uint(sqrt_rn32(x)) != __float_as_uint((float)__dsqrt_rn((double)x))) {
+            bad++;
+            first = min(first, (uint32_t)i);
+        }
+    }
+    if (bad) {
+        atomicAdd(&res[0], (unsigned long long)bad);
+        atomicMin(&res[1], (unsigned long long)first);
+    }
 }
 
 __global__ void camera_rays_kernel(FrameConst f, mirt_ray* __restrict__ out)
@@ -3305,7 +3335,7 @@ int mirt_sphere_form_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_sphere*
                            int fast, uint32_t* out)
 {
     if (!ctx_ok(c, false, "mirt_sphere_form_pairs")) return MIRT_E_INVALID;
-    if (n < 0 || (n > 0 && (!rays || !spheres || !best || !out))) {
+    if (n < 0 || fast < 0 || fast > 3 || (n > 0 && (!rays || !spheres || !best || !out))) {
         set_error("mirt_sphere_form_pairs: invalid arguments");
         return MIRT_E_INVALID;
     }
@@ -3319,18 +3349,39 @@ int mirt_sphere_form_pairs(mirt_ctx* c, const mirt_ray* rays, const mirt_sphere*
     HIP_TRY(hipMemcpyAsync(din + rb, spheres, sb, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(din + rb + sb, best, fb, hipMemcpyHostToDevice, c->stream));
     const dim3 grid((n + 255) / 256);
-    if (fast)
-        sphere_form_pairs_kernel<true><<<grid, 256, 0, c->stream>>>((const mirt_ray*)din, (const mirt_sphere*)(din + rb),
-                                                                   (const float*)(din + rb + sb), n,
-                                                                   (uint32_t*)c->d_res);
-    else
-        sphere_form_pairs_kernel<false><<<grid, 256, 0, c->stream>>>((const mirt_ray*)din,
-                                                                    (const mirt_sphere*)(din + rb),
-                                                                    (const float*)(din + rb + sb), n,
-                                                                    (uint32_t*)c->d_res);
+    const mirt_ray* dr = (const mirt_ray*)din;
+    const mirt_sphere* ds = (const mirt_sphere*)(din + rb);
+    const float* db = (const float*)(din + rb + sb);
+    uint32_t* dout = (uint32_t*)c->d_res;
+    switch (fast) {
+    case 0: sphere_form_pairs_kernel<0><<<grid, 256, 0, c->stream>>>(dr, ds, db, n, dout); break;
+    case 1: sphere_form_pairs_kernel<1><<<grid, 256, 0, c->stream>>>(dr, ds, db, n, dout); break;
+    case 2: sphere_form_pairs_kernel<2><<<grid, 256, 0, c->stream>>>(dr, ds, db, n, dout); break;
+    default: sphere_form_pairs_kernel<3><<<grid, 256, 0, c->stream>>>(dr, ds, db, n, dout); break;
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_sqrt_form_sweep(mirt_ctx* c, uint64_t* mismatches, uint32_t* first)
+{
+    if (!ctx_ok(c, false, "mirt_sqrt_form_sweep")) return MIRT_E_INVALID;
+    if (!mismatches || !first) {
+        set_error("mirt_sqrt_form_sweep: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    const int rc = ensure(&c->d_res, &c->res_cap, 16);
+    if (rc) return rc;
+    unsigned long long res[2] = {0ull, ~0ull};
+    HIP_TRY(hipMemcpyAsync(c->d_res, res, sizeof(res), hipMemcpyHostToDevice, c->stream));
+    sqrt_form_sweep_kernel<<<8192, 256, 0, c->stream>>>((unsigned long long*)c->d_res);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(res, c->d_res, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *mismatches = res[0];
+    *first = (uint32_t)res[1];
     return MIRT_OK;
 }
 

@@ -15,6 +15,7 @@
 
 #include "../../include/mirt.h"
 #include "coop.h"
+#include "exact_t.h"
 #include "layout.h"
 #include "rng.h"
 
@@ -131,13 +132,27 @@ __device__ __forceinline__ NodeV load_node_lane(const DNode* base, uint32_t i)
     return n;
 }
 
+// vec3.c:22's len = (float)sqrt((double)sq) is the correctly rounded binary32
+// root of the float sq: the binary64 root is correctly rounded to p' = 53
+// bits, and rounding a square root first to p' >= 2p + 2 = 50 bits and then to
+// p = 24 gives the directly rounded result (Figueroa: the root of a p-bit
+// number cannot lie that close to a p-bit rounding midpoint; zero, infinity and
+// NaN map to themselves either way, a subnormal sq is only a scaled normal one).
+// So the binary32 root serves -- in the spelling this toolchain rounds
+// correctly: sqrtf under HIP's default correctly rounded fp32 sqrt (the
+// Makefile does not turn it off), equal to the binary64 form on all 2^32 bit
+// patterns (scripts/sqrt_exhaustive.hip; tests/test_normalize_sqrt.py checks
+// the non-negative half in the suite). __fsqrt_rn is NOT that on gfx950: it
+// differs on 323 M patterns (MEASUREMENTS.md §C).
+__device__ __forceinline__ float sqrt_rn32(float x) { return __builtin_sqrtf(x); }
+
 // vec3.c:21-24: len = (float)sqrt((double)(x*x + y*y + z*z)); divide by len.
 __device__ __forceinline__ void normalize3(float& x, float& y, float& z)
 {
     float sq = x * x;
     sq = sq + y * y;
     sq = sq + z * z;
-    const float len = (float)__dsqrt_rn((double)sq);
+    const float len = sqrt_rn32(sq);
     if (len != 0.0f) {
         x = x / len;
         y = y / len;
@@ -458,8 +473,20 @@ __device__ __forceinline__ SphRay sph_ray(const Ray& r) { return {r.ox, r.oy, r.
 // 1/(2a) below the normal range 0: the first turns t' - M and t' + M into NaN,
 // which decide nothing; the second needs |b| > 2^105 for a t above EPS, where
 // b b overflows and disc is inf or NaN -- NaN again, or the miss hit.c sees.)
+//
+// A hit the estimate cannot rule out needs t's bits. exact_t.h computes them
+// from float pairs with the same two seeds (s', 1/(2a)) and v_rcp_f32(s'), and
+// CERTIFIES the result against a proven bound on its distance from the double
+// before the final cast (2^-39 (|b| + s') / 2a, absolute, since -b - s' may
+// cancel): certified, it is hit.c:28's t bit for bit; otherwise -- one hit in
+// some thousands of a scene's: t too near a rounding midpoint for that bound, a power of
+// two, or operands outside 2^+-30 -- the binary64 expression itself runs, as before.
+// The two forms lie side by side (the f64 one under `!cert` alone), and the
+// pair holds nothing across the walk.
+// CERT = false (mirt_sphere_form_pairs, fast = 2 only): certification off, so
+// that every surviving pair takes the f64 branch.
 // `exact` (instrumented builds only): set when the f64 path ran.
-template <bool FAST>
+template <bool FAST, bool CERT = true>
 __device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best, bool* exact = nullptr)
 {
     const float ocx = r.ox - s.x, ocy = r.oy - s.y, ocz = r.oz - s.z;
@@ -467,16 +494,21 @@ __device__ __forceinline__ float sphere_t(const SphRay& r, float4 s, float best,
     const float c = dot3(ocx, ocy, ocz, ocx, ocy, ocz) - s.w * s.w;
     const float disc = b * b - r.a4() * c;
     if (!(disc > 0.0f)) return -1.0f;
+    float t = 0.0f;
+    bool cert = false;
     if (FAST) {
         const float sq = __builtin_amdgcn_sqrtf(disc);
         const float te = (-b - sq) * r.inv2a();
         const float m = (fabsf(b) + sq) * fabsf(r.inv2a()) * 0x1p-18f;
         if ((te - m > best || te + m <= kEps) && disc >= 0x1p-126f) return -1.0f;
+        if (CERT) cert = exact_t_pair(b, disc, 2.0f * r.a(), sq, __builtin_amdgcn_rcpf(sq), r.inv2a(), t);
     }
-    // hit.c:28 in double: (-b - sqrt(disc)) / (2a), rounded to float
-    if (exact) *exact = true;
-    const double num = (double)(-b) - __dsqrt_rn((double)disc);
-    const float t = (float)__ddiv_rn(num, r.a2());
+    if (!cert) {
+        // hit.c:28 in double: (-b - sqrt(disc)) / (2a), rounded to float
+        if (exact) *exact = true;
+        const double num = (double)(-b) - __dsqrt_rn((double)disc);
+        t = (float)__ddiv_rn(num, r.a2());
+    }
     return (t > kEps && t <= best) ? t : -1.0f;
 }
 

@@ -752,7 +752,10 @@ class Renderer:
     def sphere_form_pairs(self, rays, spheres, best, fast=True):
         """float32 per pair: what the walks' sphere test returns for a best hit
         so far of best[i] (t if sphere i would become the closest hit, else
-        -1), from the filtered test (fast) or the exact one."""
+        -1), from the filtered test (fast = 1 / True) or the exact one (0).
+        fast = 2: the filtered test with the float-pair certification off;
+        fast = 3: 1.4e-45 (the bits of 1) where fast = 1 ran the binary64
+        branch, 0 elsewhere -- view the result as uint32 (include/mirt.h)."""
         rays = np.ascontiguousarray(rays, abi.RAY)
         spheres = np.ascontiguousarray(spheres, abi.SPHERE)
         best = np.ascontiguousarray(best, np.float32)
@@ -761,6 +764,14 @@ class Renderer:
         check(self.L.mirt_sphere_form_pairs(self.h, ptr(rays), ptr(spheres), ptr(best), len(rays), int(fast),
                                             ptr(out)), "mirt_sphere_form_pairs")
         return out.view(np.float32)
+
+    def sqrt_form_sweep(self):
+        """mirt_sqrt_form_sweep: (mismatches, least mismatching bit pattern) of
+        normalize3's binary32 root against the binary64 form over every
+        non-negative finite float."""
+        bad, first = C.c_uint64(), C.c_uint32()
+        check(self.L.mirt_sqrt_form_sweep(self.h, C.byref(bad), C.byref(first)), "mirt_sqrt_form_sweep")
+        return bad.value, first.value
 
     def hemisphere_probe(self, keys, k0, normals, need, out_dir):
         """mirt_hemisphere_probe: the kernels' wave-cooperative bounce sampling

@@ -665,8 +665,14 @@ int mirt_pixel_rows(int width, int shard_rows, int samples, int row_block, int s
    mirt_box_form_pairs: out[i] = 1 if `form` passes box i for ray i.
    mirt_sphere_form_pairs: out[i] = the bits of the float the sphere test
    returns for a best hit so far of best[i] (t when the sphere would become
-   the closest hit, else -1), from the filtered test (fast != 0) or the exact
-   one. */
+   the closest hit, else -1), from the exact test (fast = 0) or the filtered
+   one of the walks (fast = 1). The filtered test takes t from float pairs
+   (csrc/exact_t.h) and runs the binary64 expression only for the hit in some
+   thousands it cannot certify, so two further values exist for the tests alone,
+   compiled into this entry point's kernel only: fast = 2 is the filtered test
+   with certification off -- every pair the filter leaves takes the binary64
+   branch -- and fast = 3 returns, instead of t, 1 where fast = 1 ran the
+   binary64 branch for the pair and 0 elsewhere. */
 enum { MIRT_BOX_FORM_SLAB = 0,        /* leaf / node boxes: reciprocal filter, exact when undecided */
        MIRT_BOX_FORM_SLAB_BOX = 1,    /* the same with the pruning test for zero-component rays */
        MIRT_BOX_FORM_CONS = 2,        /* inner boxes: conservative, with margins */
@@ -678,6 +684,18 @@ int mirt_box_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_aabb *bo
                         int form, int32_t *out);
 int mirt_sphere_form_pairs(mirt_ctx *ctx, const mirt_ray *rays, const mirt_sphere *spheres, const float *best,
                            int n, int fast, uint32_t *out);
+/* csrc/exact_t.h on the host (needs no ctx and makes no HIP call): for each of
+   n triples (b, disc, d2a = 2a of hit.c:22-25, disc > 0) and caller-given seeds
+   s ~ sqrt(disc), rs ~ 1/s, rd ~ 1/d2a, th[i] = the float-pair t and
+   certified[i] = 1 where it is certified to equal hit.c:28's t (else 0, th[i]
+   without meaning). */
+int mirt_exact_t_pairs(int64_t n, const float *b, const float *disc, const float *d2a, const float *s,
+                       const float *rs, const float *rd, float *th, uint8_t *certified);
+/* normalize3's binary32 square root against vec3.c:22's (float)sqrt((double)x)
+   on every non-negative finite float, in one launch: the number of bit
+   patterns whose results differ (expected 0) and the least of them
+   (0xffffffff: none). */
+int mirt_sqrt_form_sweep(mirt_ctx *ctx, uint64_t *mismatches, uint32_t *first);
 /* The device build's partition kernels on caller-given keys (needs no scene):
    nseg segments [seg[k], seg[k+1]) of centre[0,n) (seg non-decreasing, within
    [0, n]), each partitioned by centre < split[k] as bvh.c:172-201's swap loop

@@ -101,7 +101,9 @@ def main():
                     fmaps[fname] = function_map(os.path.join(CSRC, fname))
                 fn = fmaps.get(fname, {}).get(loc[1], os.path.basename(fname)) if fname in fmaps else os.path.basename(fname)
             counts[fn][classify(op)] += 1
-    classes = ["valu", "salu", "vmem_rd", "vmem_wr", "lds", "smem", "branch_wait", "other"]
+            if op.startswith("v_") and "_f64" in op:  # binary64 VALU (also counted under valu)
+                counts[fn]["valu_f64"] += 1
+    classes = ["valu", "valu_f64", "salu", "vmem_rd", "vmem_wr", "lds", "smem", "branch_wait", "other"]
     total = collections.Counter()
     rows = sorted(counts.items(), key=lambda kv: -kv[1]["valu"])
     print(f"{'function':32s} " + " ".join(f"{c:>8s}" for c in classes))

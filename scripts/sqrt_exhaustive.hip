@@ -1,8 +1,9 @@
-// Why trace.h normalize3 keeps the binary64 square root: over all 2^32
-// binary32 bit patterns, the binary32 spellings of sqrt (__fsqrt_rn, sqrtf,
-// __builtin_sqrtf) against the binary64 root rounded to binary32 (vec3.c:22's
-// (float)sqrt((double)x), which equals the correctly rounded binary32 root),
-// compiled with the product's flags. Prints the mismatch count of each
+// Which binary32 square root trace.h normalize3 may take (sqrt_rn32: it uses
+// __builtin_sqrtf, variant 2): over all 2^32 binary32 bit patterns, the
+// binary32 spellings of sqrt (__fsqrt_rn, sqrtf, __builtin_sqrtf) against the
+// binary64 root rounded to binary32 (vec3.c:22's (float)sqrt((double)x), which
+// equals the correctly rounded binary32 root), compiled with the product's
+// flags. (tests/test_normalize_sqrt.py runs the non-negative half in the suite.) Prints the mismatch count of each
 // binary32 spelling and up to 8 mismatching inputs; exit status 0 iff the
 // spelling named by argv[1] has none.
 #include <hip/hip_runtime.h>
