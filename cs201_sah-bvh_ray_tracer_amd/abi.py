@@ -114,6 +114,12 @@ class BuildStats(C.Structure):
                 ("device_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class BuildFinishStats(C.Structure):
+    """mirt_build_finish_stats"""
+    _fields_ = [("range", C.c_int32), ("round", C.c_int32), ("subtrees", C.c_int32), ("nodes", C.c_int32),
+                ("moved", C.c_int32), ("finish_ms", C.c_float)]
+
+
 class SceneBuildStats(C.Structure):
     """mirt_scene_build_stats"""
     _fields_ = [("on_device", C.c_int32), ("levels", C.c_int32), ("nodes", C.c_int32),
@@ -203,6 +209,7 @@ SIGNATURES = [
     ("mirt_scene_upload_flat", I, [P, P, I, P, I]),
     ("mirt_bvh_build_flat_device", I, [P, P, I, I, I, C.POINTER(P), C.POINTER(I)]),
     ("mirt_last_build_stats", I, [P, P]),
+    ("mirt_last_build_finish", I, [P, P]),
     ("mirt_build_partition_probe", I, [P, P, I, P, I, P, P]),
     ("mirt_scene_layout", C.c_int64, [P, I, P, I, I, P, C.c_size_t, P]),
     ("mirt_scene_build_device", I, [P, P, I, I, I, I, P]),
@@ -299,6 +306,7 @@ OPT_TRAVERSAL, OPT_FAST_SLAB, OPT_BLOCK_WAVES, OPT_DEFER, OPT_BOUNCE_THRESHOLD, 
 OPT_BOUNCE_BLOCKS, OPT_QUAD_DRAIN, OPT_LEAF_BATCH, OPT_QUAD_BATCH, OPT_ZERO_COPY = 9, 11, 14, 15, 17
 OPT_QUEUE_ORDER, OPT_DEBUG_STALL_MS = 18, 19
 OPT_CONFIRM_ONCE, OPT_DEBUG_FAIL_CONFIRM = 21, 22
+OPT_BUILD_FINISH = 23     # the device build's finish: 0 never, 1 automatic (default), 2..64 = F
 BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4

@@ -25,6 +25,12 @@
 //              place of the left element it meets). Left ranks come from one
 //              prefix sum over the array, chains are resolved by pointer
 //              doubling, ceil(log2(longest range)) rounds.
+// The finish (MIRT_OPT_BUILD_FINISH): once a level's read-back
+// shows that no open node holds more than F <= 64 spheres, the level loop
+// stops and one wave per open node builds that node's whole subtree, one
+// sphere per lane, by the same rules (subtree_kernel). It runs twice: pass A
+// orders the spheres and counts each subtree's nodes, pass B, after the sizes
+// and pre-order indices of the levels above, writes the nodes where they belong.
 // Then subtree sizes bottom-up, pre-order indices top-down, and the nodes are
 // written in mirt_node layout. The download of the result is a separate step:
 // mirt_scene_build_device (scene_device.hip) takes the tree where it lies.
@@ -71,7 +77,7 @@ constexpr int kSmall = 32;                   // inner nodes of at most this many
 // `left`, and the output order comes from sizes and pre-order indices.
 struct BNode {
     int lo, hi;      // range of the device sphere array
-    int left;        // global index of the left child (right = left + 1); -1: leaf
+    int left;        // global index of the left child (right = left + 1); -1: leaf; kFinishRoot: subtree_kernel's
     int axis;
     int klo[3], khi[3];  // bounds as ordered keys
     float split;
@@ -83,8 +89,21 @@ struct BNode {
 };
 static_assert(sizeof(BNode) == 64, "BNode");
 
-// ctl words read back by the host
-enum { kCtlInner = 0, kCtlMaxRange = 1, kCtlDeclined = 2, kCtlWords = 4 };
+// ctl words read back by the host (kCtlFinNodes: 64 bits, words 4 and 5)
+enum { kCtlInner = 0, kCtlMaxRange = 1, kCtlDeclined = 2, kCtlFinNodes = 4, kCtlMoved = 6, kCtlError = 7, kCtlWords = 8 };
+
+// The finish: an open node of the hand-off level whose subtree one wave builds
+// (BNode::left), the spheres a wave takes, and the cap of its walk -- m spheres
+// at depth d make at most m * (40 - d) + 1 nodes, so a walk never reaches it.
+constexpr int kFinishRoot = -2;
+constexpr int kWave = 64;
+constexpr int kFinishCap = kWave * (kMaxDepth + 1) + 1;
+constexpr int kFinishFrames = kMaxDepth + 1;  // the nodes of one root-to-leaf path
+// MIRT_OPT_BUILD_FINISH 1 (automatic): builds of at most this many spheres take the finish. Measured
+// ahead at 10k spheres (4.3 against 6.9 ms), level at 100k, behind at 1M (64 against 41 ms), where the
+// 65k waves' redundant per-lane SAH scans cost more than the 24 level rounds they replace.
+constexpr int kFinishAutoMax = 131072;
+enum { kErrCap = 1, kErrSize = 2 };           // kCtlError bits: the walk hit kFinishCap / pass B outgrew pass A's count
 
 // float <-> int key with the same order (-0.0 < +0.0; the build declines -0.0 boxes)
 __device__ __forceinline__ int fkey(float f)
@@ -96,7 +115,18 @@ __device__ __forceinline__ float funkey(int k) { return __int_as_float(k >= 0 ? 
 
 __device__ __forceinline__ float comp(const float4& g, int axis) { return axis == 0 ? g.x : (axis == 1 ? g.y : g.z); }
 
-__device__ __forceinline__ bool goes_left(const BNode& nd, const float4& g) { return comp(g, nd.axis) < nd.split; }
+__device__ __forceinline__ bool goes_left(int axis, float split, const float4& g) { return comp(g, axis) < split; }
+__device__ __forceinline__ bool goes_left(const BNode& nd, const float4& g) { return goes_left(nd.axis, nd.split, g); }
+
+// the sphere's box fl(c -+ r) as keys (bvh.c:26-46)
+__device__ __forceinline__ void sphere_keys(const float4& g, int* kl, int* kh)
+{
+    for (int x = 0; x < 3; x++) {
+        const float c = comp(g, x);
+        kl[x] = fkey(c - g.w);
+        kh[x] = fkey(c + g.w);
+    }
+}
 
 // ---- first and last pass: the caller's 20-byte spheres <-> (centre, radius) + colour
 
@@ -228,14 +258,42 @@ __global__ void classify_kernel(BNode* nodes, int off, int cnt, int next_off, in
     if (valid && !inner) nd->left = -1;
 }
 
-// ---- binned SAH (bvh_build.cpp FlatBuilder::build)
+// ---- binned SAH (bvh_build.cpp FlatBuilder::build). The rules -- a bin word's
+// start value, the planes, a sphere's bins, the scan over the candidates -- are
+// stated once here, for the level kernels and for subtree_kernel.
+
+__device__ __forceinline__ int bin_word_init(int w) { return w < kBinLo ? 0 : (w < kBinHi ? kKeyPosInf : kKeyNegInf); }
+
+// the seven candidate planes of every axis of the box (bvh.c:150/154/158)
+__device__ __forceinline__ void split_planes(const int* klo, const int* khi, float sp[3][7])
+{
+    for (int a = 0; a < 3; a++) {
+        const float lo = funkey(klo[a]), hi = funkey(khi[a]);
+        for (int p = 0; p < 7; p++) sp[a][p] = split_plane(lo, hi, p + 1);
+    }
+}
+
+// The sphere's bin on every axis: add(bin word index, its box keys). Bin b + 1 of
+// an axis is the first plane the centre is left of (7: none), never a floor.
+template <class Add>
+__device__ __forceinline__ void bin_sphere(const float4& g, const float sp[3][7], Add add)
+{
+    int kl[3], kh[3];
+    sphere_keys(g, kl, kh);
+    for (int a = 0; a < 3; a++) {
+        const float c = comp(g, a);
+        int b = 7;
+        for (int p = 6; p >= 0; p--)
+            if (c < sp[a][p]) b = p;
+        add(a * 8 + b, kl, kh);
+    }
+}
 
 __global__ void init_bins_kernel(int* bins, size_t words)
 {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= words) return;
-    const int w = (int)(i % kBinWords);
-    bins[i] = w < kBinLo ? 0 : (w < kBinHi ? kKeyPosInf : kKeyNegInf);
+    bins[i] = bin_word_init((int)(i % kBinWords));
 }
 
 __global__ void bin_kernel(const float4* geo, const int* nof, int n, const BNode* nodes, int next_off, int* bins)
@@ -249,7 +307,7 @@ __global__ void bin_kernel(const float4* geo, const int* nof, int n, const BNode
     // the whole workgroup sits in one leaf, or in a node the SAH kernel bins itself
     if (uni && (nodes[first].left < 0 || nodes[first].hi - nodes[first].lo <= kSmall)) return;
     if (uni) {
-        for (int w = t; w < kBinWords; w += kBlock) sh[w] = w < kBinLo ? 0 : (w < kBinHi ? kKeyPosInf : kKeyNegInf);
+        for (int w = t; w < kBinWords; w += kBlock) sh[w] = bin_word_init(w);
         __syncthreads();
     }
     int ck = -1;       // node the planes below belong to
@@ -264,24 +322,9 @@ __global__ void bin_kernel(const float4* geo, const int* nof, int n, const BNode
             if (left < 0 || nd.hi - nd.lo <= kSmall) continue;
             ck = k;
             dst = bins + (size_t)((left - next_off) >> 1) * kBinWords;
-            for (int a = 0; a < 3; a++) {
-                const float lo = funkey(nd.klo[a]), hi = funkey(nd.khi[a]);
-                for (int p = 0; p < 7; p++) sp[a][p] = split_plane(lo, hi, p + 1);
-            }
+            split_planes(nd.klo, nd.khi, sp);
         }
-        const float4 g = geo[i];
-        int kl[3], kh[3];
-        for (int x = 0; x < 3; x++) {
-            const float c = comp(g, x);
-            kl[x] = fkey(c - g.w);
-            kh[x] = fkey(c + g.w);
-        }
-        for (int a = 0; a < 3; a++) {
-            const float c = comp(g, a);
-            int b = 7;  // bin b + 1: the first plane the centre is left of (7: none)
-            for (int p = 6; p >= 0; p--)
-                if (c < sp[a][p]) b = p;
-            const int idx = a * 8 + b;
+        bin_sphere(geo[i], sp, [&](int idx, const int* kl, const int* kh) {
             if (uni) {
                 atomicAdd(&sh[idx], 1);
                 for (int x = 0; x < 3; x++) {
@@ -295,7 +338,7 @@ __global__ void bin_kernel(const float4* geo, const int* nof, int n, const BNode
                     global_max(&dst[kBinHi + idx * 3 + x], kh[x]);
                 }
             }
-        }
+        });
     }
     if (uni) {
         __syncthreads();
@@ -338,51 +381,15 @@ __device__ __forceinline__ float kbox_area(const KBox& b)
                     funkey(b.hi[2]) - funkey(b.lo[2]));
 }
 
-__global__ void sah_kernel(const float4* geo, BNode* nodes, int off, int cnt, int next_off, const int* bins)
+// The split of a node from its filled bins (bvh.c:139-170): suffix boxes, prefix
+// boxes, the first candidate of the least cost, axis-major then plane-minor;
+// no candidate below +inf leaves axis 0 at 0.0f.
+__device__ __forceinline__ void sah_split(const int* bin, const int* klo, const int* khi, int* axis, float* split)
 {
-    const int j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= cnt) return;
-    BNode& nd = nodes[off + j];
-    if (nd.left < 0) return;
-    const int* bin = bins + (size_t)((nd.left - next_off) >> 1) * kBinWords;
-    // A small node's bins are filled here, by the same rule as bin_kernel's
-    // (which skips it): for the many small nodes of the deep levels nearly
-    // every atomic would be the first touch of its word.
-    int own[kBinWords];
-    if (nd.hi - nd.lo <= kSmall) {
-        for (int w = 0; w < kBinWords; w++) own[w] = w < kBinLo ? 0 : (w < kBinHi ? kKeyPosInf : kKeyNegInf);
-        float sp[3][7];
-        for (int a = 0; a < 3; a++) {
-            const float lo = funkey(nd.klo[a]), hi = funkey(nd.khi[a]);
-            for (int p = 0; p < 7; p++) sp[a][p] = split_plane(lo, hi, p + 1);
-        }
-        for (int e = nd.lo; e < nd.hi; e++) {
-            const float4 g = geo[e];
-            int kl[3], kh[3];
-            for (int x = 0; x < 3; x++) {
-                const float c = comp(g, x);
-                kl[x] = fkey(c - g.w);
-                kh[x] = fkey(c + g.w);
-            }
-            for (int a = 0; a < 3; a++) {
-                const float c = comp(g, a);
-                int b = 7;
-                for (int p = 6; p >= 0; p--)
-                    if (c < sp[a][p]) b = p;
-                const int idx = a * 8 + b;
-                own[idx]++;
-                for (int x = 0; x < 3; x++) {
-                    own[kBinLo + idx * 3 + x] = min(own[kBinLo + idx * 3 + x], kl[x]);
-                    own[kBinHi + idx * 3 + x] = max(own[kBinHi + idx * 3 + x], kh[x]);
-                }
-            }
-        }
-        bin = own;
-    }
     float best_cost = INFINITY, best_split = 0.0f;  // bvh.c:139-141
     int best_axis = 0;
     for (int a = 0; a < 3; a++) {
-        const float lo = funkey(nd.klo[a]), hi = funkey(nd.khi[a]);
+        const float lo = funkey(klo[a]), hi = funkey(khi[a]);
         KBox right[8];
         int nr[8];
         KBox acc = kbox_empty();
@@ -406,8 +413,36 @@ __global__ void sah_kernel(const float4* geo, BNode* nodes, int off, int cnt, in
             }
         }
     }
-    nd.axis = best_axis;
-    nd.split = best_split;
+    *axis = best_axis;
+    *split = best_split;
+}
+
+__global__ void sah_kernel(const float4* geo, BNode* nodes, int off, int cnt, int next_off, const int* bins)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= cnt) return;
+    BNode& nd = nodes[off + j];
+    if (nd.left < 0) return;
+    const int* bin = bins + (size_t)((nd.left - next_off) >> 1) * kBinWords;
+    // A small node's bins are filled here, by the same rule as bin_kernel's
+    // (which skips it): for the many small nodes of the deep levels nearly
+    // every atomic would be the first touch of its word.
+    int own[kBinWords];
+    if (nd.hi - nd.lo <= kSmall) {
+        for (int w = 0; w < kBinWords; w++) own[w] = bin_word_init(w);
+        float sp[3][7];
+        split_planes(nd.klo, nd.khi, sp);
+        for (int e = nd.lo; e < nd.hi; e++)
+            bin_sphere(geo[e], sp, [&](int idx, const int* kl, const int* kh) {
+                own[idx]++;
+                for (int x = 0; x < 3; x++) {
+                    own[kBinLo + idx * 3 + x] = min(own[kBinLo + idx * 3 + x], kl[x]);
+                    own[kBinHi + idx * 3 + x] = max(own[kBinHi + idx * 3 + x], kh[x]);
+                }
+            });
+        bin = own;
+    }
+    sah_split(bin, nd.klo, nd.khi, &nd.axis, &nd.split);
 }
 
 // ---- partition (bvh.c:172-201 in closed form); also run by mirt_build_partition_probe
@@ -518,6 +553,7 @@ __global__ void size_kernel(BNode* nodes, int off, int cnt)
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= cnt) return;
     BNode& nd = nodes[off + j];
+    if (nd.left == kFinishRoot) return;  // counted by subtree_kernel's pass A
     nd.size = nd.left < 0 ? 1u : 1u + nodes[nd.left].size + nodes[nd.left + 1].size;
 }
 
@@ -526,6 +562,7 @@ __global__ void emit_kernel(BNode* nodes, int off, int cnt, int sphere0, mirt_no
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= cnt) return;
     const BNode& nd = nodes[off + j];
+    if (nd.left == kFinishRoot) return;  // subtree_kernel's pass B writes it at nd.pre, with its subtree
     const uint32_t at = nd.pre;
     mirt_node o;
     for (int a = 0; a < 3; a++) {
@@ -542,6 +579,195 @@ __global__ void emit_kernel(BNode* nodes, int off, int cnt, int sphere0, mirt_no
         nodes[nd.left + 1].pre = at + 1 + nodes[nd.left].size;
     }
     out[at] = o;
+}
+
+// ---- the finish: one wave builds the whole subtree of one open node of at most
+// kWave spheres, lane i holding the sphere at position i of the node's range.
+// A pre-order walk, left child first (bvh.c:203-204), over an explicit stack of
+// the open path's frames; every node by the rules above: keys for the bounds,
+// bin_sphere and sah_split for the plane, the partition in closed form. All
+// control flow is uniform over the wave, and waves share nothing: no workgroup
+// barrier anywhere.
+//   EMIT false (pass A): the spheres go back in final order, the subtree's node
+//        count to the open node's `size`, which becomes a kFinishRoot;
+//   EMIT true (pass B): the same walk over the spheres now in final order --
+//        bounds and bins do not depend on the order, and the partition of a
+//        partitioned range moves nothing (counted: kCtlMoved stays 0) -- writes
+//        node k of the subtree at out[pre + k].
+
+// LDS written by some lanes of the wave is read by others behind this
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int wave_min(int v)
+{
+    for (int o = kWave / 2; o; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v)
+{
+    for (int o = kWave / 2; o; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+enum { kFrLo = 0, kFrMid = 1, kFrHi = 2, kFrAt = 3, kFrStage = 4, kFrWords = 5 };
+
+template <bool EMIT>
+__global__ void __launch_bounds__(kBlock) subtree_kernel(float4* geo, uint32_t* col, BNode* nodes, int off, int cnt,
+                                                         int depth0, int sphere0, mirt_node* out, int* ctl)
+{
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ float4 xg[kWaves][kWave];  // a partition's exchange
+    __shared__ uint32_t xc[kWaves][kWave];
+    __shared__ int lpos[kWaves][kWave];   // L_k, relative to the node's range
+    __shared__ int sbin[kWaves][kBinWords];
+    __shared__ int frames[kWaves][kFinishFrames][kFrWords];
+    const int lane = threadIdx.x % kWave, w = threadIdx.x / kWave;
+    const int j = blockIdx.x * kWaves + w;
+    if (j >= cnt) return;
+    BNode& root = nodes[off + j];
+    const int root_left = root.left;
+    if (EMIT ? root_left != kFinishRoot : root_left < 0) return;
+    const int base = root.lo, m = root.hi - root.lo;
+    const uint32_t pre = EMIT ? root.pre : 0u, size = EMIT ? root.size : 0u;
+    if (m > kWave) {  // the hand-off rule keeps every open range within one wave
+        if (lane == 0) atomicOr(&ctl[kCtlError], kErrCap);
+        return;
+    }
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint32_t cl = 0;
+    if (lane < m) {
+        g = geo[base + lane];
+        cl = col[base + lane];
+    }
+    float4* wg = xg[w];
+    uint32_t* wc = xc[w];
+    int* wl = lpos[w];
+    int* bin = sbin[w];
+    int(*fr)[kFrWords] = frames[w];
+    int sp = 0, cur = 0, moved = 0, err = 0;
+    fr[0][kFrLo] = 0;
+    fr[0][kFrHi] = m;
+    fr[0][kFrStage] = 0;
+    // a node is entered, returned to after its left subtree, and left after its right one
+    for (int step = 0; sp >= 0 && step < 3 * kFinishCap; step++) {
+        const int lo = uniform(fr[sp][kFrLo]), hi = uniform(fr[sp][kFrHi]), stage = uniform(fr[sp][kFrStage]);
+        if (stage == 1) {
+            fr[sp][kFrStage] = 2;
+            fr[sp + 1][kFrLo] = uniform(fr[sp][kFrMid]);
+            fr[sp + 1][kFrHi] = hi;
+            fr[sp + 1][kFrStage] = 0;
+            sp++;
+            continue;
+        }
+        if (stage == 2) {
+            if (EMIT && lane == 0) out[pre + (uint32_t)uniform(fr[sp][kFrAt])].skip = pre + (uint32_t)cur;
+            sp--;
+            continue;
+        }
+        if (cur >= kFinishCap) {
+            err = kErrCap;
+            break;
+        }
+        if (EMIT && (uint32_t)cur >= size) {  // pass A counted fewer: nothing is written past its count
+            err = kErrSize;
+            break;
+        }
+        const int at = cur++;
+        const int n = hi - lo;
+        const bool in = lane >= lo && lane < hi;
+        int kl[3] = {kKeyPosInf, kKeyPosInf, kKeyPosInf}, kh[3] = {kKeyNegInf, kKeyNegInf, kKeyNegInf};
+        if (in) sphere_keys(g, kl, kh);
+        int klo[3], khi[3];
+        for (int a = 0; a < 3; a++) {  // one sphere: its own box, from its lane; none: the inverted box
+            klo[a] = n > 1 ? wave_min(kl[a]) : (n == 1 ? __builtin_amdgcn_readlane(kl[a], lo) : kKeyPosInf);
+            khi[a] = n > 1 ? wave_max(kh[a]) : (n == 1 ? __builtin_amdgcn_readlane(kh[a], lo) : kKeyNegInf);
+        }
+        const bool leaf = n <= 1 || depth0 + sp >= kMaxDepth;  // bvh.c:131
+        if (EMIT && lane == 0) {
+            mirt_node o;
+            for (int a = 0; a < 3; a++) {
+                o.bmin[a] = funkey(klo[a]);
+                o.bmax[a] = funkey(khi[a]);
+            }
+            o.sphere = leaf ? sphere0 + base + lo : -1;
+            o.skip = leaf ? (pre + (uint32_t)at + 1u) | (n == 0 ? MIRT_NODE_EMPTY : 0u) : 0u;  // inner: set at stage 2
+            out[pre + (uint32_t)at] = o;
+        }
+        if (leaf) {
+            sp--;
+            continue;
+        }
+        if (sp + 1 >= kFinishFrames) {  // an inner node lies above depth 40: its child has a frame
+            err = kErrCap;
+            break;
+        }
+        for (int x = lane; x < kBinWords; x += kWave) bin[x] = bin_word_init(x);
+        float pl[3][7];
+        split_planes(klo, khi, pl);
+        wave_sync();
+        if (in)
+            bin_sphere(g, pl, [&](int idx, const int* bl, const int* bh) {
+                atomicAdd(&bin[idx], 1);
+                for (int x = 0; x < 3; x++) {
+                    atomicMin(&bin[kBinLo + idx * 3 + x], bl[x]);
+                    atomicMax(&bin[kBinHi + idx * 3 + x], bh[x]);
+                }
+            });
+        wave_sync();
+        int axis;
+        float split;
+        sah_split(bin, klo, khi, &axis, &split);
+        // the partition (bvh.c:172-201 in closed form, as scatter_kernel's)
+        const bool left = in && goes_left(axis, split, g);
+        const unsigned long long mask = __ballot(left) >> lo;
+        const int p = lane - lo, nl = __popcll(mask);
+        int dst = p;
+        if (left) {
+            dst = __popcll(mask & ((1ull << p) - 1ull));
+            wl[dst] = p;
+        }
+        wave_sync();
+        if (in && !left)
+            for (int k = 0; k < kWave && dst < nl; k++) dst = wl[dst];
+        moved += __popcll(__ballot(in && dst != p));
+        if (in) {
+            wg[lo + dst] = g;
+            wc[lo + dst] = cl;
+        }
+        wave_sync();
+        if (in) {
+            g = wg[lane];
+            cl = wc[lane];
+        }
+        wave_sync();
+        fr[sp][kFrMid] = lo + nl;
+        fr[sp][kFrAt] = at;
+        fr[sp][kFrStage] = 1;
+        fr[sp + 1][kFrLo] = lo;
+        fr[sp + 1][kFrHi] = lo + nl;
+        fr[sp + 1][kFrStage] = 0;
+        sp++;
+    }
+    if (sp >= 0 && !err) err = kErrCap;  // the step bound ended the walk
+    if (!EMIT) {
+        if (lane < m) {
+            geo[base + lane] = g;
+            col[base + lane] = cl;
+        }
+        if (lane == 0) {
+            root.size = (uint32_t)cur;
+            root.left = kFinishRoot;
+            atomicAdd((unsigned long long*)&ctl[kCtlFinNodes], (unsigned long long)cur);
+        }
+    } else if (lane == 0 && moved) {
+        atomicAdd(&ctl[kCtlMoved], moved);
+    }
+    if (lane == 0 && err) atomicOr(&ctl[kCtlError], err);
 }
 
 // ---- host side
@@ -580,8 +806,11 @@ namespace mirt {
 struct BuildState {
     Buf aos, geo[2], col[2], nof[2], rank, tsum, jump, nodes, bins, ctl, out;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t evf[4] = {nullptr, nullptr, nullptr, nullptr};  // around the finish's pass A and pass B
     mirt_build_stats stats{};
     bool have_stats = false;
+    mirt_build_finish_stats fin{};  // of the last device build, whichever entry point ran it
+    bool have_fin = false;
 };
 
 void build_state_free(BuildState* st)
@@ -592,6 +821,8 @@ void build_state_free(BuildState* st)
         if (b->p) (void)hipFree(b->p);
     if (st->ev0) (void)hipEventDestroy(st->ev0);
     if (st->ev1) (void)hipEventDestroy(st->ev1);
+    for (hipEvent_t e : st->evf)
+        if (e) (void)hipEventDestroy(e);
     delete st;
 }
 
@@ -613,8 +844,9 @@ int get_state(mirt_ctx* c, BuildState** out)
         *slot = st;  // owned by the ctx from here on
         HIP_TRY(hipEventCreate(&st->ev0));
         HIP_TRY(hipEventCreate(&st->ev1));
+        for (hipEvent_t& e : st->evf) HIP_TRY(hipEventCreate(&e));
     }
-    if (!(*slot)->ev0 || !(*slot)->ev1) {
+    if (!(*slot)->ev0 || !(*slot)->ev1 || !(*slot)->evf[3]) {
         mirt::set_error("mirt device build: the context's build state could not be set up");
         return MIRT_E_DEVICE;
     }
@@ -677,12 +909,20 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
 {
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
     *declined = 0;
+    st.have_fin = false;
+    // MIRT_OPT_BUILD_FINISH: the longest open range the finish takes (0: off); automatic: a whole
+    // wave up to kFinishAutoMax spheres, off beyond (MEASUREMENTS.md E)
+    const int opt = mirt::ctx_build_finish(c);
+    const int F = opt == 1 ? (n <= kFinishAutoMax ? kWave : 0) : opt;
+    mirt_build_finish_stats fin{};
+    fin.range = F;
+    fin.round = -1;
     int rc = ensure_spheres(st, n);
     if (!rc) rc = ensure(st.aos, (size_t)std::max(total, 1) * sizeof(mirt_sphere));
     if (!rc) rc = ensure(st.nodes, ((size_t)2 * (size_t)n + 64) * sizeof(BNode));
     if (rc) return rc;
     int* ctl = (int*)st.ctl.p;
-    int h_ctl[kCtlWords] = {0, 0, 0, 0};
+    int h_ctl[kCtlWords] = {};
     int cur = 0;
     HIP_TRY(hipMemsetAsync(ctl, 0, kCtlWords * 4, s));
     if (total > 0 && d_src) {
@@ -702,6 +942,8 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
         HIP_TRY(hipStreamSynchronize(s));
         if (h_ctl[kCtlDeclined]) {
             *declined = 1;
+            st.fin = fin;
+            st.have_fin = true;
             return MIRT_OK;
         }
     }
@@ -727,6 +969,12 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
             mirt::set_error("mirt_bvh_build_flat_device: the tree exceeds 2^31 nodes");
             return MIRT_E_INVALID;
         }
+        // the hand-off: every open node of this level fits one wave of the finish
+        if (F > 0 && d >= 0 && h_ctl[kCtlMaxRange] <= F) {
+            fin.round = (int)level_off.size() - 1;
+            fin.subtrees = inner;
+            break;
+        }
         // the next level, sized from the count just read
         const size_t have = (size_t)off + (size_t)cnt;
         rc = ensure(st.nodes, (have + 2 * (size_t)inner) * sizeof(BNode), s, have * sizeof(BNode));
@@ -746,7 +994,32 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
         off += cnt;
         cnt = 2 * inner;
     }
-    const size_t total_nodes = (size_t)off + (size_t)cnt;
+    size_t total_nodes = (size_t)off + (size_t)cnt;
+    const unsigned fin_grid = blocks((size_t)cnt * kWave, kBlock);  // one wave per node of the hand-off level
+    if (fin.round >= 0) {
+        // pass A: the spheres in final order, every subtree's node count; the total sizes the output
+        HIP_TRY(hipEventRecord(st.evf[0], s));
+        subtree_kernel<false><<<fin_grid, kBlock, 0, s>>>((float4*)st.geo[cur].p, (uint32_t*)st.col[cur].p,
+                                                          (BNode*)st.nodes.p, off, cnt, depth + fin.round, sphere0,
+                                                          nullptr, ctl);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(st.evf[1], s));
+        HIP_TRY(hipMemcpyAsync(h_ctl, ctl, kCtlWords * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h_ctl[kCtlError]) {
+            mirt::set_error("mirt device build: a subtree walk of the finish reached its cap (code %d)",
+                            h_ctl[kCtlError]);
+            return MIRT_E_DEVICE;
+        }
+        unsigned long long fin_nodes = 0;
+        std::memcpy(&fin_nodes, &h_ctl[kCtlFinNodes], 8);
+        total_nodes = total_nodes - (size_t)fin.subtrees + (size_t)fin_nodes;
+        if (fin_nodes > (unsigned long long)INT32_MAX || total_nodes > (size_t)INT32_MAX) {
+            mirt::set_error("mirt_bvh_build_flat_device: the tree exceeds 2^31 nodes");
+            return MIRT_E_INVALID;
+        }
+        fin.nodes = (int)fin_nodes;
+    }
     rc = ensure(st.out, total_nodes * sizeof(mirt_node));
     if (rc) return rc;
     BNode* nodes = (BNode*)st.nodes.p;
@@ -756,11 +1029,36 @@ int device_build(mirt_ctx* c, BuildState& st, const mirt_sphere* spheres, int to
     for (int l = 0; l < nl; l++)
         emit_kernel<<<blocks(level_cnt[l], kBlock), kBlock, 0, s>>>(nodes, level_off[l], level_cnt[l], sphere0,
                                                                    (mirt_node*)st.out.p);
+    if (fin.round >= 0) {
+        // pass B: every finish root knows its place now; the subtrees are written there
+        HIP_TRY(hipEventRecord(st.evf[2], s));
+        subtree_kernel<true><<<fin_grid, kBlock, 0, s>>>((float4*)st.geo[cur].p, (uint32_t*)st.col[cur].p, nodes, off,
+                                                         cnt, depth + fin.round, sphere0, (mirt_node*)st.out.p, ctl);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(st.evf[3], s));
+    }
     if (n > 0)
         finish_kernel<<<blocks(n, kBlock), kBlock, 0, s>>>((const float4*)st.geo[cur].p, (const uint32_t*)st.col[cur].p,
                                                           n, aos);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev1, s));
+    if (fin.round >= 0) {
+        // the control words of pass B, read once with the result
+        HIP_TRY(hipMemcpyAsync(h_ctl, ctl, kCtlWords * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        fin.moved = h_ctl[kCtlMoved];
+        if (h_ctl[kCtlError] || fin.moved) {
+            mirt::set_error("mirt device build: pass B of the finish disagrees with pass A (code %d, %d spheres moved)",
+                            h_ctl[kCtlError], fin.moved);
+            return MIRT_E_DEVICE;
+        }
+        float a = 0.0f, b = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&a, st.evf[0], st.evf[1]));
+        HIP_TRY(hipEventElapsedTime(&b, st.evf[2], st.evf[3]));
+        fin.finish_ms = a + b;
+    }
+    st.fin = fin;
+    st.have_fin = true;
     *out_count = (int)total_nodes;
     *levels_out = nl;
     return MIRT_OK;
@@ -899,6 +1197,21 @@ int mirt_last_build_stats(mirt_ctx* c, mirt_build_stats* out)
         return MIRT_E_INVALID;
     }
     *out = st->stats;
+    return MIRT_OK;
+}
+
+int mirt_last_build_finish(mirt_ctx* c, mirt_build_finish_stats* out)
+{
+    if (!c || !out) {
+        mirt::set_error("mirt_last_build_finish: null context or output");
+        return MIRT_E_INVALID;
+    }
+    const BuildState* st = *mirt::ctx_build_state(c);
+    if (!st || !st->have_fin) {
+        mirt::set_error("mirt_last_build_finish: no device build has finished on this context");
+        return MIRT_E_INVALID;
+    }
+    *out = st->fin;
     return MIRT_OK;
 }
 

@@ -35,6 +35,7 @@ int validate_flat(const mirt_node* nd, int nn, int num_spheres, int sphere_lo, c
 int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
                          uint32_t** d_display, const char* fn, bool independent = false);
 int ctx_device(const mirt_ctx* c);
+int ctx_build_finish(const mirt_ctx* c);  // MIRT_OPT_BUILD_FINISH as stored: 0 off, 1 automatic, 2..64 = F
 // bvh_device.hip: the device builder's scratch and statistics, kept on the ctx
 // (created by the first build, released by mirt_destroy).
 struct BuildState;

@@ -1670,6 +1670,7 @@ struct mirt_ctx {
     int debug_stall_ms = 0;     // MIRT_OPT_DEBUG_STALL_MS: test hook, each frame starts behind a bounded wait
     int confirm_once = 2;       // MIRT_OPT_CONFIRM_ONCE: the bounce lane loop confirms a walk's closest hit once: 0 off, 1 on, 2 auto
     int debug_fail_confirm = 0; // MIRT_OPT_DEBUG_FAIL_CONFIRM: test hook, confirmations of pixels % N == 0 fail
+    int build_finish = 1;       // MIRT_OPT_BUILD_FINISH: the device build's one-wave-per-subtree finish: 0 off, 1 auto, 2..64 = F
     mirt::BuildState* build = nullptr;  // mirt_bvh_build_flat_device's scratch (bvh_device.hip)
     mirt_scene_build_stats scene_stats{};  // of the last mirt_scene_build_device
     bool have_scene_stats = false;
@@ -2551,6 +2552,7 @@ int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_d
     return enqueue_frame(c, cam, fd, d_out, d_display, fn, independent);
 }
 int ctx_device(const mirt_ctx* c) { return c->device; }
+int ctx_build_finish(const mirt_ctx* c) { return c->build_finish; }
 BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
 {
@@ -3474,6 +3476,10 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         if (value < 0) break;
         c->debug_fail_confirm = value;
         return MIRT_OK;
+    case MIRT_OPT_BUILD_FINISH:
+        if (value < 0 || value > 64) break;
+        c->build_finish = value;
+        return MIRT_OK;
     case MIRT_OPT_QUEUE_ORDER:
         if (value < 0 || value > 2) break;
         c->queue_order = value;
@@ -3511,6 +3517,7 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_DEBUG_STALL_MS) return c->debug_stall_ms;
     if (option == MIRT_OPT_CONFIRM_ONCE) return confirm_once(c) ? 1 : 0;  // in effect for the uploaded scene
     if (option == MIRT_OPT_DEBUG_FAIL_CONFIRM) return c->debug_fail_confirm;
+    if (option == MIRT_OPT_BUILD_FINISH) return c->build_finish;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
     set_error("mirt_get_option: bad option %d", option);
     return MIRT_E_INVALID;

@@ -341,6 +341,16 @@ class Renderer:
         check(self.L.mirt_last_build_stats(self.h, C.byref(st)), "mirt_last_build_stats")
         return {k: getattr(st, k) for k, _ in abi.BuildStats._fields_}
 
+    def last_build_finish(self):
+        """mirt_build_finish_stats of this context's last device build
+        (build_bvh, build_scene or a rebuilding update_scene), as a dict: range
+        (F in effect, 0: off), round (the level round at which one wave per
+        open node took over, -1: it did not), subtrees, nodes, moved (always
+        0), finish_ms."""
+        st = abi.BuildFinishStats()
+        check(self.L.mirt_last_build_finish(self.h, C.byref(st)), "mirt_last_build_finish")
+        return {k: getattr(st, k) for k, _ in abi.BuildFinishStats._fields_}
+
     def build_scene(self, spheres, start=0, end=None, depth=0):
         """Spheres in, scene resident (mirt_scene_build_device): the tree of
         spheres[start:end] is built and laid out on this context's device and

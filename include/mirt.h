@@ -251,6 +251,25 @@ typedef struct mirt_build_stats {
 /* Of the ctx's last finished mirt_bvh_build_flat_device (MIRT_E_INVALID: none). */
 int mirt_last_build_stats(mirt_ctx *ctx, mirt_build_stats *out);
 
+/* The finish of the device build (MIRT_OPT_BUILD_FINISH): the build runs level
+   by level, round 0 at `depth`, until a round's open (inner) nodes all hold at
+   most F spheres; one wave per open node then builds that node's whole subtree.
+   `levels` of mirt_build_stats and mirt_scene_build_stats counts the rounds run
+   level by level: round + 1 when the finish ran. */
+typedef struct mirt_build_finish_stats {
+    int32_t range;      /* F in effect for the build (0: finish off) */
+    int32_t round;      /* host-loop round at which the finish took over; -1: it did not run */
+    int32_t subtrees;   /* open inner nodes handed to it */
+    int32_t nodes;      /* tree nodes it wrote (roots included) */
+    int32_t moved;      /* spheres pass B would have moved: always 0 */
+    float   finish_ms;  /* HIP-event time of the finish passes */
+} mirt_build_finish_stats;
+/* Of the ctx's last finished device build, whichever entry point ran it
+   (mirt_bvh_build_flat_device, mirt_scene_build_device, the rebuild of
+   mirt_scene_update_device[_ptr]); a declined input reports round -1.
+   MIRT_E_INVALID, before any HIP call: NULL ctx or out, or no build has run. */
+int mirt_last_build_finish(mirt_ctx *ctx, mirt_build_finish_stats *out);
+
 /* ------------------------------ device: spheres in, scene resident (mirt 0.8) */
 
 /* Build and lay out a scene on the device of ctx in one call: the tree of
@@ -861,10 +880,19 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        spheres, not separable at 100k), else 0.
                                        mirt_get_option reads back 0/1: in effect for the scene.
                                        Speed only. */
-       MIRT_OPT_DEBUG_FAIL_CONFIRM = 22 /* test hook: N > 0 = that one test reports failure for
+       MIRT_OPT_DEBUG_FAIL_CONFIRM = 22, /* test hook: N > 0 = that one test reports failure for
                                        every chain whose pixel index is a multiple of N although
                                        the box passed, so the second walk runs on ordinary
-                                       scenes (same frames, slower); 0 (default) = off */ };
+                                       scenes (same frames, slower); 0 (default) = off */
+       MIRT_OPT_BUILD_FINISH = 23   /* device build: once the longest open range of a level is at
+                                       most F spheres, one wave per open node builds the node's
+                                       whole subtree in one launch instead of a level at a time
+                                       (mirt_last_build_finish): 0 = never, 2..64 = F,
+                                       1 (default) = automatic: F = 64 for a build of at most
+                                       131,072 spheres (measured ahead at 10k spheres, level at
+                                       100k), else 0 (behind at 1M). Every other value is
+                                       MIRT_E_INVALID; mirt_get_option reads back the stored
+                                       value. Speed only: the same bytes under every setting. */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back

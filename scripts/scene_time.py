@@ -15,6 +15,11 @@ byte for byte and scalar for scalar, with path A's of the same round (not
 timed). C's build_ms / layout_ms split comes from mirt_scene_build_stats.
 Render scenes are built as (0, n, 0), the benchmark scene as benchmark.c:317
 builds it, (0, n - 1, 20). One JSON line per shape.
+
+--finish 0,16,32,64 (the default) runs path C once per value of
+MIRT_OPT_BUILD_FINISH in every round (C_f0_ms, C_f16_ms, ...: the call, its
+build_ms and the finish's finish_ms); C itself and path B run under the
+library's default. A library without the option (MIRT_LIB) runs no such arms.
 """
 import argparse
 import ctypes as C
@@ -51,8 +56,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="render:10000,render:100000,render:1000000,bench:1000000")
+    ap.add_argument("--finish", default="0,16,32,64", help="MIRT_OPT_BUILD_FINISH values, one arm of path C each")
     a = ap.parse_args()
     L = mirt.load()
+    arms = [int(f) for f in a.finish.split(",")] if hasattr(L, "mirt_last_build_finish") else []
     p = abi.ptr
     clock = time.perf_counter
 
@@ -69,6 +76,8 @@ def main():
                 scene, rng = mirt.create_benchmark_spheres(n, 1), (0, n - 1, 20)
             t = {k: [] for k in ("A", "A_build", "A_upload", "B", "B_build", "B_upload", "C", "C_build", "C_layout",
                                  "upload_host", "upload_device")}
+            for f in arms:
+                t.update({f"C_f{f}": [], f"C_f{f}_build": [], f"C_f{f}_finish": []})
             stats = None
             for rep in range(a.reps + 1):          # rep 0: warm-up
                 ms = {}
@@ -137,6 +146,22 @@ def main():
                 bad = same_layout(r.resident_layout(), ref)
                 if bad or reordered.tobytes() != sa.tobytes() or sc.tobytes() != scene.tobytes():
                     raise SystemExit(f"{shape}: path C's scene differs from A's: {bad or 'spheres'}")
+                # C again, once per finish setting
+                for f in arms:
+                    r.set_option(abi.OPT_BUILD_FINISH, f)
+                    t0 = clock()
+                    rc = L.mirt_scene_build_device(r.h, p(sc), n, *rng, p(reordered))
+                    t1 = clock()
+                    r.set_option(abi.OPT_BUILD_FINISH, 1)
+                    if rc:
+                        fail(shape, "mirt_scene_build_device", rc)
+                    bad = same_layout(r.resident_layout(), ref)
+                    if bad or reordered.tobytes() != sa.tobytes():
+                        raise SystemExit(f"{shape}: path C's scene with finish {f} differs from A's: {bad or 'spheres'}")
+                    ms[f"C_f{f}"] = t1 - t0
+                    if rep:
+                        t[f"C_f{f}_build"].append(r.last_scene_build_stats()["build_ms"])
+                        t[f"C_f{f}_finish"].append(r.last_build_finish()["finish_ms"])
                 if rep:
                     for k, v in ms.items():
                         t[k].append(v * 1e3)

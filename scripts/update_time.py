@@ -21,6 +21,11 @@ for byte and scalar for scalar, with the host's (not timed), the quality with
 mirt_bvh_quality_flat's, the permutation with reordered == spheres[perm]. One
 JSON line per shape.
 
+--finish 0,16,32,64 (the default) runs UC once more per value of
+MIRT_OPT_BUILD_FINISH in every round (UC_f0_ms, UC_f16_ms, ...), checked the
+same way; every other call runs under the library's default. A library
+without the option (MIRT_LIB) runs no such arms.
+
 Then frame time against decay: the blocking 1920x1080 depth-5 frame of
 `--frame-spheres` render spheres whose centres have diffused by N(0, sigma), on
 the refit scene and on a rebuild of the same spheres (median of `reps` frames
@@ -74,8 +79,10 @@ def main():
     ap.add_argument("--shapes", default="render:10000,render:100000,render:1000000")
     ap.add_argument("--frame-spheres", type=int, default=10000)
     ap.add_argument("--frame-sigmas", default="0,1,3,10")
+    ap.add_argument("--finish", default="0,16,32,64", help="MIRT_OPT_BUILD_FINISH values, one arm of UC each")
     a = ap.parse_args()
     L = mirt.load()
+    arms = [int(f) for f in a.finish.split(",")] if hasattr(L, "mirt_last_build_finish") else []
     p = abi.ptr
     clock = time.perf_counter
 
@@ -99,7 +106,7 @@ def main():
             s = scene.copy()
             nodes = mirt.build_bvh(s, *rng).nodes          # s: the scene's order from here on
             base = mirt.bvh_quality(nodes, n)["cost"]
-            t = {k: [] for k in ("Q", "R", "UR", "C", "UC")}
+            t = {k: [] for k in ["Q", "R", "UR", "C", "UC"] + [f"UC_f{f}" for f in arms]}
             decays = []
             for rep in range(a.reps + 1):          # rep 0: warm-up
                 s2 = moved(s, a.sigma, rep)
@@ -153,18 +160,23 @@ def main():
                 ms["C"] = (clock() - t0) * 1e3
                 must(shape, "mirt_scene_build_device", rc)
                 differs(shape, "mirt_scene_build_device's scene", same_layout(r.resident_layout(), want_build))
-                # UC
-                original(True)
-                t0 = clock()
-                rc = L.mirt_scene_update_device(r.h, p(s2), n, start, end, 1e-9, p(out), p(perm), C.byref(res))
-                ms["UC"] = (clock() - t0) * 1e3
-                must(shape, "mirt_scene_update_device", rc)
-                bad = same_layout(r.resident_layout(), want_build)
-                if not bad and (not res.rebuilt or not res.on_device or out.tobytes() != host.tobytes()
-                                or out.tobytes() != s2[perm].tobytes()
-                                or res.installed.cost != mirt.bvh_quality(rebuilt, n)["cost"]):
-                    bad = "the result"
-                differs(shape, "the rebuild branch", bad)
+                # UC, under the default and once per finish setting
+                for f in [None] + arms:
+                    original(True)
+                    if f is not None:
+                        r.set_option(abi.OPT_BUILD_FINISH, f)
+                    t0 = clock()
+                    rc = L.mirt_scene_update_device(r.h, p(s2), n, start, end, 1e-9, p(out), p(perm), C.byref(res))
+                    ms["UC" if f is None else f"UC_f{f}"] = (clock() - t0) * 1e3
+                    if f is not None:
+                        r.set_option(abi.OPT_BUILD_FINISH, 1)
+                    must(shape, "mirt_scene_update_device", rc)
+                    bad = same_layout(r.resident_layout(), want_build)
+                    if not bad and (not res.rebuilt or not res.on_device or out.tobytes() != host.tobytes()
+                                    or out.tobytes() != s2[perm].tobytes()
+                                    or res.installed.cost != mirt.bvh_quality(rebuilt, n)["cost"]):
+                        bad = "the result"
+                    differs(shape, f"the rebuild branch (finish {f})", bad)
                 if rep:
                     for k, v in ms.items():
                         t[k].append(v)
