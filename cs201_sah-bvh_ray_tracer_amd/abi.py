@@ -101,6 +101,13 @@ class PrimaryPlanes(C.Structure):
     _fields_ = [("t", C.c_void_p), ("sphere", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class PrimaryCacheStats(C.Structure):
+    """mirt_primary_cache_stats"""
+    _fields_ = [("hits", C.c_uint64), ("fills", C.c_uint64), ("bypassed", C.c_uint64), ("scene_id", C.c_uint64),
+                ("bytes", C.c_uint64), ("valid", C.c_int32), ("last", C.c_int32), ("reason", C.c_int32),
+                ("width", C.c_int32), ("rows", C.c_int32)]
+
+
 class Counts(C.Structure):
     """mirt_counts"""
     _fields_ = [("rays", C.c_uint64), ("nodes", C.c_uint64), ("spheres", C.c_uint64), ("hits", C.c_uint64),
@@ -265,6 +272,9 @@ SIGNATURES = [
     ("mirt_bounce_stats", I, [P, P, P, P, I]),
     ("mirt_set_option", I, [P, I, I]),
     ("mirt_get_option", I, [P, I]),
+    ("mirt_primary_cache_stats_get", I, [P, P]),
+    ("mirt_primary_cache_read", I, [P, P, P, C.c_size_t]),
+    ("mirt_primary_cache_write", I, [P, P, P, C.c_size_t]),
     # include/mirt_dropin.h: the per-ray surface
     ("mirt_dropin_init", I, [I, I, I]),
     ("mirt_dropin_release", None, []),
@@ -307,6 +317,12 @@ OPT_BOUNCE_BLOCKS, OPT_QUAD_DRAIN, OPT_LEAF_BATCH, OPT_QUAD_BATCH, OPT_ZERO_COPY
 OPT_QUEUE_ORDER, OPT_DEBUG_STALL_MS = 18, 19
 OPT_CONFIRM_ONCE, OPT_DEBUG_FAIL_CONFIRM = 21, 22
 OPT_BUILD_FINISH = 23     # the device build's finish: 0 never, 1 automatic (default), 2..64 = F
+OPT_PRIMARY_CACHE = 24    # a still camera's frames start from the stored primary hits: 0 off (default), 1 on
+# mirt_primary_cache_stats: `last` (how the last frame met the cache) and `reason` (why it was no hit)
+PCACHE_BYPASS, PCACHE_FILL, PCACHE_HIT = 0, 1, 2
+PCACHE_KIND = {PCACHE_BYPASS: "bypass", PCACHE_FILL: "fill", PCACHE_HIT: "hit"}
+PCACHE_REASON = {0: "", 1: "EMPTY", 2: "SCENE", 3: "CAMERA", 4: "GEOMETRY", 5: "OFF", 6: "SCHEDULE", 7: "JITTER",
+                 8: "PLANES"}
 BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4

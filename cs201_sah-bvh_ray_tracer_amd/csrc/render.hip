@@ -14,6 +14,7 @@
 #include <mutex>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "coop.h"
@@ -359,6 +360,10 @@ struct BounceRec {
 // PLANES (as for render_kernel): with planes, the lane that owns a pixel
 // stores its closest hit where the walk returns it; a pixel handed to a
 // deferred wave is stored by that wave's lane 0 (render_pixel).
+// PLANES = CacheFill / CacheRead (ORD only; the primary cache, trace.h): the
+// walk's hit of each frame-0 pixel also goes to the cache, or comes from it
+// with no walk at all. Tile mapping and queue grouping are the kernel's own, so
+// the bounce pass receives the queue a walked frame gives it.
 template <bool FAST, bool ORD, bool BND = false, class... PLANES>
 // Register budget of the ordered camera-packet kernel (ORD): 8 waves per SIMD (64 VGPRs;
 // 67 and 7 waves without the attribute). With four frames in flight
@@ -380,6 +385,9 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
                                                       BounceRec* __restrict__ queue, uint32_t* __restrict__ qctl,
                                                       int octants = 1, PLANES... planes)
 {
+    constexpr bool kFill = (std::is_same_v<PLANES, CacheFill> || ... || false);
+    constexpr bool kRead = (std::is_same_v<PLANES, CacheRead> || ... || false);
+    static_assert(ORD || !(kFill || kRead), "the primary cache belongs to the ordered camera-packet kernel");
     __shared__ uint32_t cstack[ORD ? 1 : kMaxDepth * 256];
     Counters cnt{0, 0, 0, 0, 0};
     const int wave = threadIdx.x >> 6;
@@ -392,15 +400,17 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
         if (threadIdx.x == 0) gdone = 0;
         __syncthreads();
     }
-    if (!ORD && (int)blockIdx.x < dfr.blocks) {  // zero-component camera rays: whole path in this wave
-        const uint32_t n = __builtin_amdgcn_readfirstlane(*dfr.count);
-        const uint32_t stride = (uint32_t)(dfr.blocks * 4);
-        for (uint32_t j = blockIdx.x * 4 + wave; j < n; j += stride) {
-            const uint32_t p = __builtin_amdgcn_readfirstlane(dfr.list[j]);
-            render_pixel<FAST, false>(sc, f, (int)(p % f.width), (int)(p / f.width), lane == 0, false,
-                                                     out, acc, cnt, cstack + threadIdx.x, 256, nullptr, planes...);
+    if constexpr (!ORD) {
+        if ((int)blockIdx.x < dfr.blocks) {  // zero-component camera rays: whole path in this wave
+            const uint32_t n = __builtin_amdgcn_readfirstlane(*dfr.count);
+            const uint32_t stride = (uint32_t)(dfr.blocks * 4);
+            for (uint32_t j = blockIdx.x * 4 + wave; j < n; j += stride) {
+                const uint32_t p = __builtin_amdgcn_readfirstlane(dfr.list[j]);
+                render_pixel<FAST, false>(sc, f, (int)(p % f.width), (int)(p / f.width), lane == 0, false,
+                                                         out, acc, cnt, cstack + threadIdx.x, 256, nullptr, planes...);
+            }
+            return;
         }
-        return;
     }
     const int tile = (blockIdx.x - dfr.blocks) * 4 + wave;
     int x, r;
@@ -429,12 +439,26 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
     if (!ORD && dfr.blocks > 0 && alive && slab_ray(ray).generic) alive = false;  // traced by a deferred wave
     float t;
     int s;
-    if constexpr (ORD) {
+    if constexpr (kRead) {
+        // the stored hit of the pixel's frame-0 twin: launch row r is row
+        // r - j * shard_rows of frame j (8x8 tiles straddle frames; in the
+        // 4x4x4 packets that is yr), j by row_sample's division
+        t = 0.0f;
+        s = -1;
+        if (alive) {
+            int cr = r;
+            if (f.samples > 1) cr -= (int)magic_div((uint32_t)r, (uint32_t)f.shard_rows, f.magic.shard_rows) * f.shard_rows;
+            (load_cached(planes, (size_t)cr * f.width + x, t, s), ...);
+        }
+    } else if constexpr (ORD) {
         closest_packet_ordered<FAST, false, BND>(sc, ray, alive, t, s, cnt);
     } else
         closest_hit<true, FAST, false>(sc, ray, alive, t, s, cnt);
     const size_t i = (size_t)r * f.width + x;
-    if constexpr (sizeof...(PLANES) > 0) {
+    if constexpr (kFill) {
+        // frame 0's lanes only (j == 0 in the 4x4x4 packets): the cache holds one slab
+        if (alive && r < f.shard_rows) (store_planes(planes, i, sc, ray, t, s), ...);
+    } else if constexpr (!kRead && sizeof...(PLANES) > 0) {
         if (alive) (store_planes(planes, i, sc, ray, t, s), ...);
     }
     bool push = false;
@@ -1606,6 +1630,35 @@ struct SceneSlot {
     bool have_base_cost = false;  // dropped by every install of a scene
 };
 
+// What the camera rays of a frame and its pixel -> row map are computed from:
+// the FrameConst fields camera_ray and shard_row_to_y read (jitter aside: a
+// jittered frame never meets the cache), and the identity of the scene.
+// Compared bitwise, so -0.0 and +0.0 differ: a miss, the safe side.
+struct PrimaryKey {
+    float cam[12];               // px .. vz
+    float aspect, wf, hf;
+    int width, height, row_block, shard, num_shards, lead_skip, shard_rows;
+    uint64_t scene_id;           // mirt_ctx_scene_id at enqueue
+};
+
+// The primary cache of a ctx (MIRT_OPT_PRIMARY_CACHE): one slab of
+// (t, sphere), t first, in one allocation that only ever grows.
+// No events of its own: frames of one ctx never overlap -- a launch on another
+// stream than the previous one first waits for `done` (launch_render) -- so a
+// fill's stores, a hit's loads and the next fill's stores are ordered as the
+// frames are, whichever streams they run on.
+struct PrimaryCache {
+    int on = 0;
+    void* d = nullptr;
+    size_t cap = 0;
+    bool valid = false;          // d holds the hits of `key`
+    PrimaryKey key{};
+    mirt_camera cam{};           // the caller's camera of the key: tells CAMERA from GEOMETRY (reason only)
+    uint64_t hits = 0, fills = 0, bypassed = 0;
+    int last = MIRT_PCACHE_BYPASS, reason = MIRT_PCACHE_OFF;
+    size_t pixels() const { return (size_t)key.shard_rows * key.width; }
+};
+
 struct mirt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1661,6 +1714,8 @@ struct mirt_ctx {
     Planes planes;              // mirt_render_frame_planes*: the planes of the frame being enqueued
     void* d_planes = nullptr;   // planes of the blocking / async forms, copied to the host behind the frame
     size_t planes_cap = 0;
+    PrimaryCache pc;            // MIRT_OPT_PRIMARY_CACHE: the camera rays' hits of a still camera
+    mirt_camera frame_cam{};    // the camera of the frame being enqueued (pc's reason)
     int queue_order = 0;        // MIRT_OPT_QUEUE_ORDER: 0 auto (tile order for lone_frame), 1 octants, 2 tile order
     uint32_t* d_defer = nullptr;  // [count, list...]
     size_t defer_cap = 0;
@@ -1944,11 +1999,34 @@ bool ctx_ok(mirt_ctx* c, bool need_scene, const char* fn)
 
 bool has_planes(const Planes& pl) { return pl.t || pl.sphere || pl.normal; }
 
+// How one frame meets the ctx's primary cache: MIRT_PCACHE_*, and the slab.
+struct PrimaryUse {
+    int how = MIRT_PCACHE_BYPASS;
+    float* t = nullptr;
+    int32_t* sphere = nullptr;
+};
+
 // The camera-packet kernel of a frame, with the planes' stores if it has any.
+// pcu: how the frame meets the ctx's primary cache (pc_classify) -- a hit runs
+// the one cached form (no walk: bounded and unbounded are the same kernel), a
+// fill the walk that also stores frame 0's hits.
 template <bool FAST, bool ORD, bool BND>
 void launch_primary(int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f, uint32_t* d_out, float* d_acc,
-                    Deferred dfr, BounceRec* queue, uint32_t* qctl, int octants, const Planes& pl)
+                    Deferred dfr, BounceRec* queue, uint32_t* qctl, int octants, const Planes& pl,
+                    const PrimaryUse& pcu = PrimaryUse{})
 {
+    if constexpr (FAST && ORD) {
+        if (pcu.how == MIRT_PCACHE_HIT) {
+            primary_kernel<true, true, false><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants,
+                                                                     CacheRead{pcu.t, pcu.sphere});
+            return;
+        }
+        if (pcu.how == MIRT_PCACHE_FILL) {
+            primary_kernel<true, true, BND><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants,
+                                                                   CacheFill{pcu.t, pcu.sphere});
+            return;
+        }
+    }
     if (has_planes(pl))
         primary_kernel<FAST, ORD, BND><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants, pl);
     else
@@ -2001,6 +2079,8 @@ int launch_render(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_ac
     HIP_TRY(hipEventRecord(c->done, s));
     c->last_stream = s;
     c->launched = true;
+    // a fill is the cache's content once every call of its launch has succeeded
+    if (c->pc.on && c->pc.last == MIRT_PCACHE_FILL) c->pc.valid = true;
     return MIRT_OK;
 }
 
@@ -2012,9 +2092,67 @@ bool camera_bounded(const mirt_ctx* c, const FrameConst& f)
     return origin_within_4c(scene_of(c)->o_bound, o);
 }
 
+// MIRT_OPT_PRIMARY_CACHE: the frame being enqueued is a bypass, a hit or a
+// fill, decided here on the host. diag: a counting or diagnostic
+// launch. Eligible is exactly the frame for which launch_render_body picks
+// primary_kernel<true, true, *>, without jitter and without planes; the
+// reasons are looked for in the order of the enum. A fill whose slab outgrows
+// the allocation waits for the frames that may still read it, then grows it
+// (the rule of d_planes): no allocation on a hit or a same-size fill.
+int pc_classify(mirt_ctx* c, const FrameConst& f, bool diag, PrimaryUse* use)
+{
+    PrimaryCache& pc = c->pc;
+    *use = PrimaryUse{};
+    if (!pc.on) return MIRT_OK;
+    const bool packet = c->trav == kTravWavefront && f.use_bvh && f.depth >= 1 && !diag && c->fast_slab &&
+                        dev_scene(c).ordered && f.num_rows > 0 && f.width > 0;
+    const int why = !packet ? MIRT_PCACHE_SCHEDULE : f.jitter ? MIRT_PCACHE_JITTER
+                    : has_planes(c->planes) ? MIRT_PCACHE_PLANES : 0;
+    if (why) {
+        pc.bypassed++;
+        pc.last = MIRT_PCACHE_BYPASS;
+        pc.reason = why;
+        return MIRT_OK;
+    }
+    PrimaryKey k;
+    std::memset(&k, 0, sizeof k);
+    std::memcpy(k.cam, &f.px, sizeof k.cam);
+    k.aspect = f.aspect; k.wf = f.wf; k.hf = f.hf;
+    k.width = f.width; k.height = f.height; k.row_block = f.row_block; k.shard = f.shard;
+    k.num_shards = f.num_shards; k.lead_skip = f.lead_skip; k.shard_rows = f.shard_rows;
+    k.scene_id = scene_of(c)->id;
+    if (pc.valid && !std::memcmp(&k, &pc.key, sizeof k)) {
+        pc.hits++;
+        pc.last = MIRT_PCACHE_HIT;
+        pc.reason = 0;
+    } else {
+        const int reason = !pc.valid ? MIRT_PCACHE_EMPTY : k.scene_id != pc.key.scene_id ? MIRT_PCACHE_SCENE
+                           : std::memcmp(&c->frame_cam, &pc.cam, sizeof pc.cam) ? MIRT_PCACHE_CAMERA
+                                                                                : MIRT_PCACHE_GEOMETRY;
+        pc.valid = false;   // until the launch is enqueued (launch_render)
+        const size_t bytes = 8 * (size_t)k.shard_rows * k.width;
+        if (bytes > pc.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+            if (int rc = ensure(&pc.d, &pc.cap, bytes)) return rc;
+        }
+        pc.key = k;
+        pc.cam = c->frame_cam;
+        pc.fills++;
+        pc.last = MIRT_PCACHE_FILL;
+        pc.reason = reason;
+    }
+    use->how = pc.last;
+    use->t = (float*)pc.d;
+    use->sphere = (int32_t*)pc.d + pc.pixels();
+    return MIRT_OK;
+}
+
 int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s, bool timed,
                        mirt_counts* d_counts, uint32_t* d_wave_stats, uint64_t* d_bdiag, AccumShare* chain)
 {
+    PrimaryUse pcu;
+    if (int rc = pc_classify(c, f, d_counts || d_wave_stats || d_bdiag, &pcu)) return rc;
     const int tiles = ((f.width + 7) / 8) * ((f.num_rows + 7) / 8);
     const int bw = c->block_waves;
     const int blocks = (tiles + bw - 1) / bw;
@@ -2097,9 +2235,9 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const int ptiles = f.samples >= 4 ? ((f.width + 3) / 4) * ((f.shard_rows + 3) / 4) * ((f.samples + 3) / 4)
                                           : tiles;
         if (camera_bounded(c, f))
-            launch_primary<true, true, true>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes);
+            launch_primary<true, true, true>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes, pcu);
         else
-            launch_primary<true, true, false>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes);
+            launch_primary<true, true, false>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes, pcu);
         HIP_TRY(hipGetLastError());
         if (int rc2 = fold()) return rc2;
         if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
@@ -2122,9 +2260,9 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const size_t blds = bounce_lds_bytes(f.depth);
         const int oq = octant_queue(c);
         if (c->fast_slab && sc.ordered && camera_bounded(c, f))
-            launch_primary<true, true, true>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
+            launch_primary<true, true, true>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes, pcu);
         else if (c->fast_slab && sc.ordered)
-            launch_primary<true, true, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
+            launch_primary<true, true, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes, pcu);
         else if (c->fast_slab)
             launch_primary<true, false, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes);
         else
@@ -2268,7 +2406,7 @@ void mirt_destroy(mirt_ctx* c)
     mirt::build_state_free(c->build);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
-                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes})
+                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->pc.d})
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2451,6 +2589,7 @@ int mirt_render_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_fra
         return MIRT_E_NOSCENE;
     }
     const FrameConst f = make_frame_const(cam, fd);
+    c->frame_cam = *cam;
     return launch_render(c, f, d_out, d_acc, (hipStream_t)stream, false, nullptr);
 }
 
@@ -2500,6 +2639,7 @@ int enqueue_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd
     // slabs, then the last one folded as a fresh frame, so the (possibly
     // shared) accumulation buffer holds what a sequence of fresh frames leaves
     const bool raw = independent && f.samples > 1 && !f.accumulate;
+    c->frame_cam = *cam;
     rc = launch_render(c, f, d_out, raw ? nullptr : c->acc->d_acc, c->stream, true, nullptr);
     if (rc) return rc;
     *d_display = d_out + (size_t)(f.samples - 1) * pixels;
@@ -3492,6 +3632,19 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         if (value != 1 && value != 2 && value != 4 && value != 8) break;
         c->block_waves = value;
         return MIRT_OK;
+    case MIRT_OPT_PRIMARY_CACHE:
+        if (value != 0 && value != 1) break;
+        if (value == 0 && c->pc.d) {
+            // the frames that may still read or fill the slab, on whichever stream
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+            (void)hipFree(c->pc.d);
+        }
+        if (value == 0) c->pc = PrimaryCache{};
+        c->pc.on = value;
+        c->pc.hits = c->pc.fills = c->pc.bypassed = 0;   // counted since the option was last set to 1
+        return MIRT_OK;
     default:
         break;
     }
@@ -3518,9 +3671,78 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_CONFIRM_ONCE) return confirm_once(c) ? 1 : 0;  // in effect for the uploaded scene
     if (option == MIRT_OPT_DEBUG_FAIL_CONFIRM) return c->debug_fail_confirm;
     if (option == MIRT_OPT_BUILD_FINISH) return c->build_finish;
+    if (option == MIRT_OPT_PRIMARY_CACHE) return c->pc.on;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
     set_error("mirt_get_option: bad option %d", option);
     return MIRT_E_INVALID;
+}
+
+int mirt_primary_cache_stats_get(mirt_ctx* c, mirt_primary_cache_stats* out)
+{
+    if (!c || !out) {
+        set_error("mirt_primary_cache_stats_get: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    const PrimaryCache& pc = c->pc;
+    *out = mirt_primary_cache_stats{};
+    out->hits = pc.hits;
+    out->fills = pc.fills;
+    out->bypassed = pc.bypassed;
+    out->scene_id = pc.valid ? pc.key.scene_id : 0;
+    out->bytes = pc.cap;
+    out->valid = pc.valid ? 1 : 0;
+    out->last = pc.last;
+    out->reason = pc.reason;
+    out->width = pc.valid ? pc.key.width : 0;
+    out->rows = pc.valid ? pc.key.shard_rows : 0;
+    return MIRT_OK;
+}
+
+// What the two slab calls check before any HIP call.
+static bool pc_slab_args_ok(const mirt_ctx* c, const void* t, const void* sphere, size_t n, const char* fn)
+{
+    if (!c || !t || !sphere || !c->pc.valid || n != c->pc.pixels()) {
+        set_error("%s: invalid arguments, or no valid cache of that size", fn);
+        return false;
+    }
+    return true;
+}
+
+// The frames that may still fill or read the slab have ended.
+static int pc_settle(mirt_ctx* c)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+    return MIRT_OK;
+}
+
+int mirt_primary_cache_read(mirt_ctx* c, float* t, int32_t* sphere, size_t n)
+{
+    if (!pc_slab_args_ok(c, t, sphere, n, "mirt_primary_cache_read")) return MIRT_E_INVALID;
+    if (int rc = pc_settle(c)) return rc;
+    HIP_TRY(hipMemcpy(t, c->pc.d, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sphere, (const char*)c->pc.d + 4 * n, 4 * n, hipMemcpyDeviceToHost));
+    return MIRT_OK;
+}
+
+int mirt_primary_cache_write(mirt_ctx* c, const float* t, const int32_t* sphere, size_t n)
+{
+    if (!pc_slab_args_ok(c, t, sphere, n, "mirt_primary_cache_write")) return MIRT_E_INVALID;
+    // a hit frame indexes the scene's arrays with what the slab holds. The
+    // bound is the resident scene's: a hit implies that it is the key's (scene
+    // ids never recur), and a slab of any other scene is never read again
+    const int ns = scene_of(c)->num_spheres;
+    for (size_t i = 0; i < n; i++)
+        if (sphere[i] < -1 || sphere[i] >= ns || (sphere[i] >= 0 && !(std::isfinite(t[i]) && t[i] > 0.0f))) {
+            set_error("mirt_primary_cache_write: element %zu (t %g, sphere %d) is no hit of the resident scene", i,
+                      (double)t[i], sphere[i]);
+            return MIRT_E_INVALID;
+        }
+    if (int rc = pc_settle(c)) return rc;
+    HIP_TRY(hipMemcpy(c->pc.d, t, 4 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((char*)c->pc.d + 4 * n, sphere, 4 * n, hipMemcpyHostToDevice));
+    return MIRT_OK;
 }
 
 }  // extern "C"

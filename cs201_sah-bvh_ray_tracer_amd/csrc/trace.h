@@ -1684,6 +1684,36 @@ struct Planes {
     float* normal = nullptr;
 };
 
+// The primary cache of a ctx (MIRT_OPT_PRIMARY_CACHE; render.hip PrimaryCache):
+// the camera rays' closest hits of ONE slab (shard_rows * width elements,
+// indexed like a one-frame colour output), t = 0 and sphere = -1 on a miss --
+// the values store_planes writes. As element types of the camera-packet
+// kernel's trailing pack they select, next to Planes, two further forms of it:
+// CacheFill, whose walk also stores frame 0's hits, and CacheRead, which
+// starts from the stored hits instead of the walk.
+struct CacheFill {
+    float* t;
+    int32_t* sphere;
+};
+struct CacheRead {
+    const float* t;
+    const int32_t* sphere;
+};
+
+// Frame 0's hit (t, s) of cache element i, as the walk left it.
+__device__ __forceinline__ void store_planes(const CacheFill& pc, size_t i, const DevScene&, const Ray&, float t, int s)
+{
+    pc.t[i] = s >= 0 ? t : 0.0f;
+    pc.sphere[i] = s >= 0 ? s : -1;
+}
+
+// The hit of cache element i, in place of the walk's (t, s).
+__device__ __forceinline__ void load_cached(const CacheRead& pc, size_t i, float& t, int& s)
+{
+    t = pc.t[i];
+    s = pc.sphere[i];
+}
+
 // One pixel's element of the planes.
 struct PlaneSlot {
     Planes pl;

@@ -275,6 +275,17 @@ class HostBuffer:
             pass
 
 
+def primary_cache_stats(handle):
+    """mirt_primary_cache_stats of a mirt_ctx handle (a Renderer's .h, or
+    MultiRenderer.ctx(lane, rank)), as a dict with "last" and "reason" named."""
+    st = abi.PrimaryCacheStats()
+    check(load().mirt_primary_cache_stats_get(handle, C.byref(st)), "mirt_primary_cache_stats_get")
+    out = _fields(st)
+    out["last"] = abi.PCACHE_KIND[st.last]
+    out["reason"] = abi.PCACHE_REASON[st.reason]
+    return out
+
+
 class Renderer:
     """One device context (mirt_ctx) with a resident scene."""
 
@@ -642,6 +653,30 @@ class Renderer:
     def get_option(self, option):
         return check(self.L.mirt_get_option(self.h, option), "mirt_get_option")
 
+    def primary_cache_stats(self):
+        """mirt_primary_cache_stats of this context (abi.OPT_PRIMARY_CACHE), as
+        a dict; "last" is "hit" / "fill" / "bypass" and "reason" the name of
+        why the last frame was no hit ("" on a hit)."""
+        return primary_cache_stats(self.h)
+
+    def primary_cache_read(self):
+        """The cache's slab (mirt_primary_cache_read): (t float32, sphere int32),
+        each of shape (rows, width)."""
+        st = self.primary_cache_stats()
+        t = np.zeros((st["rows"], st["width"]), np.float32)
+        sphere = np.zeros((st["rows"], st["width"]), np.int32)
+        check(self.L.mirt_primary_cache_read(self.h, ptr(t), ptr(sphere), t.size), "mirt_primary_cache_read")
+        return t, sphere
+
+    def primary_cache_write(self, t, sphere):
+        """Replace the cache's slab (mirt_primary_cache_write; a test hook: a
+        hit frame then starts from these hits)."""
+        t = np.ascontiguousarray(t, np.float32)
+        sphere = np.ascontiguousarray(sphere, np.int32)
+        if t.size != sphere.size:
+            raise MirtError(f"primary_cache_write: {t.size} t values for {sphere.size} sphere indices")
+        check(self.L.mirt_primary_cache_write(self.h, ptr(t), ptr(sphere), t.size), "mirt_primary_cache_write")
+
     def bounce_stats(self, cam, width, height, depth=5, seed=1, sample=0, shard=0, num_shards=1):
         """Per-wave diagnostic of the bounce kernel: uint64 array of (iterations,
         walking lanes summed, iterations after the queue ran dry, their lanes,
@@ -873,6 +908,10 @@ class MultiRenderer:
     def ctx(self, lane, rank):
         """(lane, rank)'s mirt_ctx handle (owned by the multi renderer)."""
         return self.L.mirt_multi_ctx(self.h, lane, rank)
+
+    def primary_cache_stats(self, lane, rank):
+        """mirt_primary_cache_stats of (lane, rank)'s context."""
+        return primary_cache_stats(self.ctx(lane, rank))
 
     def phase_log(self, lane, rank, n):
         """mirt_phase_log of (lane, rank)'s context: [primary_ms, bounce_ms] of its last n frames."""

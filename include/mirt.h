@@ -884,7 +884,7 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        every chain whose pixel index is a multiple of N although
                                        the box passed, so the second walk runs on ordinary
                                        scenes (same frames, slower); 0 (default) = off */
-       MIRT_OPT_BUILD_FINISH = 23   /* device build: once the longest open range of a level is at
+       MIRT_OPT_BUILD_FINISH = 23,  /* device build: once the longest open range of a level is at
                                        most F spheres, one wave per open node builds the node's
                                        whole subtree in one launch instead of a level at a time
                                        (mirt_last_build_finish): 0 = never, 2..64 = F,
@@ -892,7 +892,16 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        131,072 spheres (measured ahead at 10k spheres, level at
                                        100k), else 0 (behind at 1M). Every other value is
                                        MIRT_E_INVALID; mirt_get_option reads back the stored
-                                       value. Speed only: the same bytes under every setting. */ };
+                                       value. Speed only: the same bytes under every setting. */
+       MIRT_OPT_PRIMARY_CACHE = 24  /* a still camera (main.c:379-408's accumulating loop): 1 = the
+                                       ctx keeps the camera rays' closest hits (t, sphere) of one
+                                       slab, 8 bytes per shard pixel, and a frame whose camera
+                                       rays are those of the frame that stored them starts from
+                                       them instead of walking the tree (below:
+                                       mirt_primary_cache_stats); 0 (default) = off: waits for the
+                                       ctx's frames and releases the memory. Every other value is
+                                       MIRT_E_INVALID; mirt_get_option reads back the stored
+                                       value. Speed only: the same bytes under either setting. */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back
@@ -903,6 +912,62 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
 enum { MIRT_TRAV_TILE = 0, MIRT_TRAV_WAVEFRONT = 5, MIRT_TRAV_WAVEFRONT_V02 = 1 /* deprecated alias */ };
 int mirt_set_option(mirt_ctx *ctx, int option, int value);
 int mirt_get_option(mirt_ctx *ctx, int option);
+
+/* MIRT_OPT_PRIMARY_CACHE 1: every frame the ctx enqueues (mirt_render_frame,
+   _device, _async, and the frames mirt_multi issues on it) is classified on
+   the host when it is enqueued.
+     BYPASS: the frame runs exactly as with the option off; the cache is neither
+       read nor written and stays valid if it was. First reason found, in this
+       order: SCHEDULE -- the frame does not run the ordered camera-packet kernel
+       (MIRT_TRAV_TILE, brute force, a tree without ordered walks,
+       MIRT_OPT_FAST_SLAB / _PRUNE / _ORDERED 0, depth 0, mirt_count_frame,
+       mirt_wave_stats, mirt_bounce_stats); JITTER -- fd->jitter; PLANES -- a
+       mirt_render_frame_planes* frame.
+     The key of every other frame, compared bitwise: what its camera rays and
+       its pixel -> row map are computed from (the camera as the frame sees it:
+       position, forward, and the horizontal and vertical spans; aspect, width,
+       height, row_block, shard, num_shards, lead_skip and the shard's rows)
+       and mirt_ctx_scene_id at enqueue. Not in the key: seed, sample, samples,
+       max_depth, accumulate, frames, the outputs, the stream, the speed options.
+     HIT: the cache is valid and holds the hits of this key. The camera pass
+       loads each pixel's (t, sphere) instead of walking; everything behind it
+       is unchanged. The stored t is the walk's t, so the frame is the walked
+       frame byte for byte.
+     FILL: every other frame. Its camera pass walks and also stores the hits
+       of its first frame; the key is recorded. First reason found, in this
+       order: EMPTY -- no valid cache; SCENE -- another scene id (every
+       install gives a new one: no install hook is needed); CAMERA -- the
+       caller's mirt_camera differs; GEOMETRY -- the frame desc does.
+   Frames of one ctx never overlap, whatever streams they run on, so the cache
+   needs no synchronisation of its own. The slab grows like the ctx's other
+   buffers: after waiting for the ctx's frames; never on a hit or a fill of the
+   same size. mirt_destroy releases it. */
+enum { MIRT_PCACHE_BYPASS = 0, MIRT_PCACHE_FILL = 1, MIRT_PCACHE_HIT = 2 };
+enum { MIRT_PCACHE_EMPTY = 1, MIRT_PCACHE_SCENE = 2, MIRT_PCACHE_CAMERA = 3, MIRT_PCACHE_GEOMETRY = 4,
+       MIRT_PCACHE_OFF = 5, /* the option is 0 (what mirt_primary_cache_stats_get then reports) */
+       MIRT_PCACHE_SCHEDULE = 6, MIRT_PCACHE_JITTER = 7, MIRT_PCACHE_PLANES = 8 };
+typedef struct mirt_primary_cache_stats {
+    uint64_t hits, fills, bypassed;   /* frames classified since the option was last set to 1 */
+    uint64_t scene_id;                /* of the key; 0 when not valid */
+    uint64_t bytes;                   /* device memory the cache holds */
+    int32_t  valid;                   /* 1: the cache holds the hits of a key */
+    int32_t  last;                    /* of the last frame enqueued: MIRT_PCACHE_HIT / _FILL / _BYPASS */
+    int32_t  reason;                  /* why it was not a hit (enum above); 0 on a hit */
+    int32_t  width, rows;             /* geometry of the slab held; 0 when not valid */
+} mirt_primary_cache_stats;
+/* No HIP call. MIRT_E_INVALID for a NULL ctx or out. */
+int mirt_primary_cache_stats_get(mirt_ctx *ctx, mirt_primary_cache_stats *out);
+/* The slab itself, for tests: rows * width elements, pixel r * width + x in
+   shard row order, t = 0 and sphere = -1 on a miss (the t and sphere planes of
+   mirt_render_frame_planes for that frame). Both calls wait for the ctx's
+   frames; both return MIRT_E_INVALID before any HIP call for a NULL argument,
+   a cache that is not valid, or n != rows * width. _write replaces the slab
+   after checking every element on the host: sphere in [-1, num_spheres) of the
+   resident scene and, where sphere >= 0, t finite and > 0; otherwise
+   MIRT_E_INVALID and nothing is written, so no slab can make a later frame
+   index out of bounds. */
+int mirt_primary_cache_read(mirt_ctx *ctx, float *t, int32_t *sphere, size_t n);
+int mirt_primary_cache_write(mirt_ctx *ctx, const float *t, const int32_t *sphere, size_t n);
 
 #ifdef __cplusplus
 }
