@@ -46,7 +46,7 @@ class Oracle:
             "o_gen_render_scene": (None, [C.c_uint, I, P]),
             "o_gen_bench_scene": (None, [C.c_uint, I, C.c_float, P]),
             "o_build": (P, [P, I, I, I]), "o_free": (None, [P]),
-            "o_node_count": (I, [P]), "o_flatten": (I, [P, P, I]),
+            "o_node_count": (I, [P]), "o_flatten": (I, [P, P, I]), "o_tree_from_flat": (P, [P, I]),
             "o_intersect": (None, [P, P, I, P, I, I, P]),
             "o_intersect_flat": (None, [P, I, P, I, P, I, P]),
             "o_sphere_pairs": (None, [P, P, I, P]), "o_aabb_pairs": (None, [P, P, I, P]),
@@ -85,6 +85,13 @@ class Oracle:
         out = np.zeros(n, abi.NODE)
         assert self.L.o_flatten(tree, _p(out), n) == n
         return out
+
+    def tree_from_flat(self, nodes):
+        """The pointer tree of a flat tree (abi.NODE array), boxes as they
+        stand: what render / trace_rays / intersect take, for a tree that no
+        builder made. flatten() of it gives `nodes` back. Release with free."""
+        nodes = np.ascontiguousarray(nodes, abi.NODE)
+        return self.L.o_tree_from_flat(_p(nodes), len(nodes))
 
     def free(self, tree):
         self.L.o_free(tree)

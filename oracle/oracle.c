@@ -285,6 +285,31 @@ int o_flatten(void *root, mirt_node *out, int cap)
     return o_flatten_rec((const ONode *)root, out, 0);
 }
 
+/* The inverse of o_flatten: the pointer tree of a flat pre-order tree (left
+   child i + 1, right child = the left child's skip), boxes copied as they
+   stand, so that o_render_rows / o_trace_rays / o_intersect take a tree that
+   no builder made. A leaf keeps its sphere index and whether it is empty
+   (count 0 or 1: all that the flat form holds). Free with o_free. */
+static ONode *o_from_flat_rec(const mirt_node *nd, uint32_t i)
+{
+    ONode *n = (ONode *)malloc(sizeof(ONode));
+    memcpy(&n->box.min, nd[i].bmin, sizeof n->box.min);
+    memcpy(&n->box.max, nd[i].bmax, sizeof n->box.max);
+    if (nd[i].sphere >= 0) {
+        n->kid[0] = n->kid[1] = NULL;
+        n->first = nd[i].sphere;
+        n->count = (nd[i].skip & MIRT_NODE_EMPTY) ? 0 : 1;
+    } else {
+        n->kid[0] = o_from_flat_rec(nd, i + 1);
+        n->kid[1] = o_from_flat_rec(nd, nd[i + 1].skip & MIRT_SKIP_MASK);
+        n->first = -1;
+        n->count = 0;
+    }
+    return n;
+}
+
+void *o_tree_from_flat(const mirt_node *nodes, int nn) { return nn > 0 ? o_from_flat_rec(nodes, 0) : NULL; }
+
 /* ---------------------------------------------------------- intersect */
 
 typedef struct { float t; V3 p, n; int hit; int sphere; } OHit;

@@ -161,6 +161,44 @@ def test_accumulate_restatement(oracle):
     assert (np.abs(half[:, :3].astype(int) - c[:, :3] // 2) <= 1).all()
 
 
+def _node_depths(flat):
+    d = np.zeros(len(flat), np.int32)
+    ends = []
+    for i in range(len(flat)):
+        while ends and ends[-1] <= i:
+            ends.pop()
+        d[i] = len(ends)
+        if flat["sphere"][i] < 0:
+            ends.append(int(flat["skip"][i] & abi.SKIP_MASK))
+    return d
+
+
+def test_tree_from_flat_round_trip(oracle, small):
+    """o_tree_from_flat is o_flatten's inverse: flatten(tree_from_flat(x)) == x
+    for the fixtures' builder trees -- among them trees with empty leaves and
+    with leaves at the builder's depth limit of 40 -- and o_intersect on the
+    rebuilt pointer tree equals o_intersect_flat on x, hit for hit."""
+    empty = deep = 0
+    keys = [f"render_{n}_{seed}" for n in (20, 100, 1000) for seed in (1, 2)] + ["bench_1000_1"]
+    for key in keys:
+        x = small[key + "_tree"]
+        empty += int(((x["skip"] & abi.NODE_EMPTY) != 0).sum())
+        # bench_1000_1 was built from depth 20 (benchmark.c:317): its leaves at depth 20 are the builder's depth 40
+        deep += int(((x["sphere"] >= 0) & (_node_depths(x) >= (20 if key.startswith("bench") else 40))).sum())
+        t = oracle.tree_from_flat(x)
+        assert oracle.L.o_node_count(t) == len(x), key
+        assert oracle.flatten(t).tobytes() == x.tobytes(), key
+        s = small[key + "_post"]
+        ns = 999 if key.startswith("bench") else len(s)
+        rays = small["hits_bench_rays"] if key.startswith("bench") else small["hits_rays"]
+        want = oracle.intersect_flat(x, s[:ns], rays)
+        got = oracle.intersect(t, s[:ns], rays)
+        oracle.free(t)
+        assert got.tobytes() == want.tobytes(), key
+    assert empty > 0 and deep > 0, (empty, deep)
+    assert oracle.tree_from_flat(np.zeros(0, abi.NODE)) is None
+
+
 def test_oracle_flat_dfs_equals_pointer_dfs(mirt, oracle, small):
     """o_intersect_flat (hit.c:91-109 over a flat tree, used for the 10M /
     100M benchmark-mode points) equals o_intersect on the oracle's own
