@@ -547,8 +547,9 @@ int issue_rank_body(mirt_multi* m, Lane& L, int r)
             // copy mode: rank 0's stream copies this rank's slabs once they are done
             MHIP(hipEventRecord(L.rendered[r], st));
             L.slabs_ready[r]->store(L.seq, std::memory_order_release);
-        } else if (m->rccl && exchange && r > 0) {
+        } else if (m->rccl && exchange && r > 0 && cnt > 0) {
             // RCCL: this rank's displays to rank 0, on the stream that rendered them
+            // (an empty shard sends nothing: rank 0's group posts no receive for a zero count)
             std::lock_guard<std::timed_mutex> lk(*m->comm_mu[r]);
             if (m->failed.load()) return failed_status(m, "mirt_multi_render_frames_async");
             MNCCL(ncclSend(src, cnt, ncclUint32, 0, m->comm[r], st));
@@ -597,7 +598,7 @@ int issue_rank_body(mirt_multi* m, Lane& L, int r)
                 MNCCL(ncclGroupEnd());
                 m->st_groups.fetch_add(1);
             } else if (!m->rccl) {
-                if (self) {   // rank 0's own slabs into its slot, as the other ranks' are copied
+                if (self && cnt) {   // rank 0's own slabs into its slot, as the other ranks' are copied
                     MHIP(hipMemcpyAsync(L.gathered + (size_t)s * J.shard_stride, src, 4 * cnt, hipMemcpyDeviceToDevice,
                                         st));
                     m->st_copies.fetch_add(1);
@@ -618,6 +619,7 @@ int issue_rank_body(mirt_multi* m, Lane& L, int r)
                     MHIP(hipStreamWaitEvent(st, L.rendered[q], 0));
                     uint32_t* to = L.gathered + (size_t)q * J.shard_stride;
                     const size_t cq = (size_t)J.sr.rows[q] * J.W * J.nframes;
+                    if (cq == 0) continue;   // an empty shard: nothing to copy
                     if (m->dev[q] == m->dev[0])
                         MHIP(hipMemcpyAsync(to, L.src[q], 4 * cq, hipMemcpyDeviceToDevice, st));
                     else
@@ -629,8 +631,9 @@ int issue_rank_body(mirt_multi* m, Lane& L, int r)
                     // other shards' slabs arrive as device copies of its own
                     // (HBM writes of the receives; no wire time, no receive kernels)
                     for (int q = 1; q < J.world; q++) {
-                        MHIP(hipMemcpyAsync(L.gathered + (size_t)q * J.shard_stride, src,
-                                            4 * std::min(cnt, (size_t)J.sr.rows[q] * J.W * J.nframes),
+                        const size_t cq = std::min(cnt, (size_t)J.sr.rows[q] * J.W * J.nframes);
+                        if (cq == 0) continue;   // an empty shard on either side
+                        MHIP(hipMemcpyAsync(L.gathered + (size_t)q * J.shard_stride, src, 4 * cq,
                                             hipMemcpyDeviceToDevice, st));
                         m->st_copies.fetch_add(1);
                     }

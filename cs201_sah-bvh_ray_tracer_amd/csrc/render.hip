@@ -1976,7 +1976,7 @@ int accum_prepare(AccumShare* a, size_t pixels, hipStream_t s)
         a->pend = nullptr;   // a frame of the old geometry: a new accumulation starts
         a->pend_ctx = nullptr;
         if (a->has_fold) HIP_TRY(hipStreamWaitEvent(s, a->folded, 0));
-        HIP_TRY(hipMemsetAsync(a->d_acc, 0, pixels * 12, s));
+        if (pixels) HIP_TRY(hipMemsetAsync(a->d_acc, 0, pixels * 12, s));   // 0: an empty shard (mirt.h)
         HIP_TRY(hipEventRecord(a->folded, s));
         a->has_fold = true;
         a->pixels = pixels;
@@ -2643,7 +2643,7 @@ int enqueue_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd
     rc = launch_render(c, f, d_out, raw ? nullptr : c->acc->d_acc, c->stream, true, nullptr);
     if (rc) return rc;
     *d_display = d_out + (size_t)(f.samples - 1) * pixels;
-    if (raw) {
+    if (raw && pixels) {   // an empty shard (mirt.h) has nothing to fold: a grid of 0 workgroups is no launch
         FrameConst f1 = f;
         f1.samples = 1;
         f1.accumulate = 0;
@@ -2678,8 +2678,9 @@ int enqueue_host_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_des
     // as a 2D copy (rows x width): the runtime takes a DMA engine for it, where a
     // 1D copy of the same bytes often runs as a blit kernel on this stream's
     // compute queue (as multi.hip does)
-    const size_t row = (size_t)fd->width * 4;
-    HIP_TRY(hipMemcpy2DAsync(out, row, disp, row, row, (size_t)shard_row_count(fd), hipMemcpyDeviceToHost, c->stream));
+    const size_t row = (size_t)fd->width * 4, rows = (size_t)shard_row_count(fd);
+    if (rows)   // an empty shard (mirt.h) writes nothing through `out`
+        HIP_TRY(hipMemcpy2DAsync(out, row, disp, row, row, rows, hipMemcpyDeviceToHost, c->stream));
     return MIRT_OK;
 }
 
@@ -2768,6 +2769,7 @@ namespace {
 uint32_t* host_mapped(const void* p, size_t bytes)
 {
     hipPointerAttribute_t a, b;
+    if (!bytes) return nullptr;   // an empty shard's output: nothing to store, and no last byte to look up
     if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeHost || !a.devicePointer ||
         hipPointerGetAttributes(&b, (const char*)p + bytes - 1) != hipSuccess || b.type != hipMemoryTypeHost ||
         (const char*)b.devicePointer != (const char*)a.devicePointer + bytes - 1) {
@@ -2856,7 +2858,8 @@ int mirt_render_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc
     if (c) c->lone_frame = false;
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    // (an empty shard records no events: last_ms stays the last timed frame's)
+    if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
 }
 
@@ -2929,7 +2932,7 @@ static int render_frame_planes_host(mirt_ctx* c, const mirt_camera* cam, const m
     }
     if (!blocking) return MIRT_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
 }
 

@@ -108,7 +108,10 @@ typedef struct mirt_frame_desc {
     int32_t shard;           /* this shard renders row blocks b with b % num_shards == shard */
     int32_t num_shards;
     int32_t samples;         /* frames rendered by this call, samples sample .. sample+samples-1 of the
-                                RNG contract (0 or 1: one). One launch covers all of them, so the
+                                RNG contract (0 or 1: one; at most 64). The sum is taken in uint32_t:
+                                frame j uses (sample + j) mod 2^32, so four frames from sample
+                                0xFFFFFFFE use 0xFFFFFFFE, 0xFFFFFFFF, 0 and 1 -- what four calls
+                                with a uint32_t counter would pass. One launch covers all of them, so the
                                 bounce pass's tail (its longest chains) is paid once, not per frame.
                                 Output: `samples` consecutive slabs, one per frame; with an
                                 accumulation buffer, the frames are folded into it in order (as
@@ -475,7 +478,28 @@ int mirt_scene_update_device_ptr(mirt_ctx *ctx, const void *d_spheres, int num_s
 
 /* ---------------------------------------------------------- rendering */
 
-/* Number of rows (and the row indices, if rows != NULL) a shard renders. */
+/* Number of rows (and the row indices, if rows != NULL) a shard renders.
+   Limits of a valid descriptor: width, height >= 1 with width * height *
+   samples <= 2^31; max_depth 0..8; samples 0..64; row_block >= 1; 0 <= shard <
+   num_shards; lead_skip 0..7, and 0 unless num_shards >= 2; frames >= 1 when
+   accumulate is set. Every seed and every sample is valid.
+   Empty shards: a valid descriptor may describe a shard without rows -- more
+   shards than the image has row blocks (height 9, row_block 8: shards 2.. of
+   3), or shard 0 sitting out a low frame under lead_skip. mirt_shard_rows
+   returns 0 for it, and every frame call (mirt_render_frame, _device, _async,
+   the three mirt_render_frame_planes calls, mirt_count_frame, and the launches
+   of mirt_multi, which deals such shards to its ranks by itself) renders it as
+   MIRT_OK:
+     - nothing is written through the colour, accumulation or plane pointers;
+       they are checked as for any other shard (non-NULL where required);
+       mirt_count_frame writes all zeros;
+     - the ctx's own accumulation buffer is treated as for any other change of
+       frame geometry: a pending accumulation ends, the next frame starts one;
+     - no kernel is launched, so mirt_last_kernel_ms keeps the value of the
+       last frame that had rows;
+     - under MIRT_OPT_PRIMARY_CACHE the frame is a BYPASS (SCHEDULE), which
+       leaves the cache as it was;
+     - the ctx stays usable for the next frame. */
 int mirt_shard_rows(const mirt_frame_desc *fd, int32_t *rows);
 
 /* The pixel loop of main.c:356-374 (fresh) / main.c:382-407 (accumulate) for

@@ -51,6 +51,38 @@ def test_distinct_devices_golden_one_lane(mirt, golden, scene10k, devices, direc
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("direct", [False, True])
+@pytest.mark.parametrize("lead_skip", [0, 2])
+def test_distinct_devices_low_frame_with_empty_ranks(gpu, mirt, scene10k, devices, direct, lead_skip):
+    """A frame with fewer row blocks than ranks (40 x 9, 8-row blocks: every
+    rank from 2 on has no rows; with the lead-skip weighting rank 0 has none
+    either): the ranks without rows send nothing -- rank 0's receive group
+    posts no receive for a zero count, so an ncclSend of 0 elements would have
+    no partner -- and the frame equals one context's, one frame and a batch of
+    three. The distinct-device send side has only ever been read, not run
+    (DESIGN section 2): this is its first run."""
+    s, b = scene10k
+    W, H = 40, 9
+    cam = mirt.default_camera()
+    gpu.upload(s, b)
+    want = [gpu.render_frame(cam, W, H, depth=5, seed=3, sample=j) for j in range(3)]
+    bufs = [mirt.HostBuffer((H, W, 4)) for _ in range(3)]
+    try:
+        with mirt.MultiRenderer(devices, host_direct=direct) as m:
+            m.set_option(mirt.abi.MULTI_OPT_LEAD_SKIP, lead_skip)
+            m.upload(s, b)
+            assert (m.render_frame(cam, W, H, depth=5, seed=3) == want[0]).all()
+            m.render_frames_async(cam, mirt.frame_desc(W, H, depth=5, seed=3, sample=0), bufs)
+            m.wait()
+            for j in range(3):
+                assert (bufs[j].array == want[j]).all(), j
+            assert (m.render_frame(cam, W, H, depth=5, seed=3) == want[0]).all()   # the object stays usable
+    finally:
+        for x in bufs:
+            x.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("direct", [False, True])
 def test_distinct_devices_lanes_in_flight(gpu, mirt, scene10k, devices, direct):
     """Three lanes, launches of four successive fresh frames (bench.py's
     N >= 4 schedule): every frame equals one context's frame of its sample."""
