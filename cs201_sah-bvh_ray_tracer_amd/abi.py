@@ -238,6 +238,8 @@ SIGNATURES = [
     ("mirt_render_frame_planes", I, [P, P, P, P, P]),
     ("mirt_render_frame_planes_device", I, [P, P, P, P, P, P, P]),
     ("mirt_render_frame_planes_async", I, [P, P, P, P, P]),
+    ("mirt_render_rays_device", I, [P, P, P, P, P, P, P]),
+    ("mirt_render_rays", I, [P, P, P, P, P]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),
@@ -322,7 +324,7 @@ OPT_PRIMARY_CACHE = 24    # a still camera's frames start from the stored primar
 PCACHE_BYPASS, PCACHE_FILL, PCACHE_HIT = 0, 1, 2
 PCACHE_KIND = {PCACHE_BYPASS: "bypass", PCACHE_FILL: "fill", PCACHE_HIT: "hit"}
 PCACHE_REASON = {0: "", 1: "EMPTY", 2: "SCENE", 3: "CAMERA", 4: "GEOMETRY", 5: "OFF", 6: "SCHEDULE", 7: "JITTER",
-                 8: "PLANES"}
+                 8: "PLANES", 9: "RAYS"}
 BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4

@@ -537,6 +537,130 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
     }
 }
 
+// ------------------------------------------------------------------------
+// Ray frames (mirt_render_rays*): a frame in every respect, except that the
+// camera ray of launch pixel i = r * width + x (the index of the colour
+// output and of the planes, computed in size_t) is rays[i], a caller's ray
+// used as given. The pixel's RNG key stays the frame's (chain_key), so the
+// bounce pass, the folds and the accumulation are the plain frame's. The
+// kernels are their own, not further instantiations of primary_kernel /
+// render_kernel: a frame without rays keeps its kernels' arguments and code.
+
+// One wave per 8x8 pixel tile, as the plain frame kernels: a tile row's eight
+// rays are 192 contiguous bytes, and the rays of neighbouring pixels are the
+// ones most likely to walk the same nodes.
+// (MIRT_RAY_TILE 0, for measurements: 64 successive pixels of a row per wave.)
+#ifndef MIRT_RAY_TILE
+#define MIRT_RAY_TILE 1
+#endif
+__device__ __forceinline__ bool ray_tile_pixel(const FrameConst& f, int& x, int& r)
+{
+    if (!MIRT_RAY_TILE) {   // the grid's lanes (64 per tile) are no fewer than the pixels
+        const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+        r = (int)(i / (size_t)f.width);
+        x = (int)(i - (size_t)r * f.width);
+        return i < (size_t)f.num_rows * f.width;
+    }
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int tiles_x = (f.width + 7) >> 3;
+    x = (tile % tiles_x) * 8 + (lane & 7);
+    r = (tile / tiles_x) * 8 + (lane >> 3);
+    return x < f.width && r < f.num_rows;
+}
+
+__device__ __forceinline__ Ray load_ray(const mirt_ray* __restrict__ rays, size_t i)
+{
+    const mirt_ray& rr = rays[i];
+    return Ray{rr.origin.x, rr.origin.y, rr.origin.z, rr.direction.x, rr.direction.y, rr.direction.z};
+}
+
+// The primary pass of a ray frame on the wavefront schedule (use_bvh, any
+// depth). Caller's rays are incoherent for all the kernel knows: each lane
+// walks its own (the walk of intersect_kernel, closest_hit<false>: four-wide
+// with an LDS stack column where the tree admits it, zero-component rays and
+// far origins included), so there are no packets and no deferred waves. Behind
+// the walk it is primary_kernel: sky, base + half black below depth 2, else the
+// first bounce into the queue (one atomic per wave, tile order) for the
+// bounce_kernel the ctx's options select. Depth 0 is black without a walk
+// (renderer.c:23-24). PLANES as for primary_kernel.
+template <bool FAST, class... PLANES>
+__global__ __launch_bounds__(256) void ray_primary_kernel(DevScene sc, FrameConst f, const mirt_ray* __restrict__ rays,
+                                                          uint32_t* __restrict__ out, float* __restrict__ acc,
+                                                          BounceRec* __restrict__ queue, uint32_t* __restrict__ qctl,
+                                                          PLANES... planes)
+{
+    __shared__ uint32_t wstack[kWideStack * kWideStride];
+    int x, r;
+    const bool alive = ray_tile_pixel(f, x, r);
+    const size_t i = alive ? (size_t)r * f.width + x : 0;
+    if (f.depth < 1) {
+        if (alive) store_pixel(f, out, acc, i, 255u << 24);
+        return;
+    }
+    const Ray ray = load_ray(rays, i);
+    Counters cnt{0, 0, 0, 0, 0};
+    float t;
+    int s;
+    // (zero-component rays: closest_hit hands each to the whole wave in turn.
+    // Keeping them in their lanes of the four-wide walk, whose exact box test
+    // cannot order or cull by distance, measured 3.3x slower on the pinhole's
+    // centre row and column and 7x slower on an orthographic frame)
+    closest_hit<false, FAST, false>(sc, ray, alive, t, s, cnt, wstack + threadIdx.x);
+    if constexpr (sizeof...(PLANES) > 0) {
+        if (alive) (store_planes(planes, i, sc, ray, t, s), ...);
+    }
+    bool push = false;
+    BounceRec rec;
+    if (alive) {
+        if (s < 0) {
+            store_pixel(f, out, acc, i, sky_rgba(ray.dy));      // renderer.c:65-70
+        } else if (f.depth < 2) {
+            store_pixel(f, out, acc, i, blend_rgba(sc.color[s], 255u << 24));
+        } else {
+            const float4 g = sc.geo[s];
+            float p[3], n[3];
+            hit_point_normal(ray, t, g, p, n);
+            uint32_t k = 0;
+            float bx, by, bz;
+            hemisphere(pixel_key(f.seed, (uint32_t)(shard_row_to_y(f, r) * f.width + x), row_sample(f, r)), k, n, bx, by,
+                       bz);
+            rec = BounceRec{p[0], p[1], p[2], bx, by, bz, (uint32_t)i, k, sc.color[s], 0u};
+            push = true;
+        }
+    }
+    const uint64_t pm = __ballot(push);
+    if (pm) {
+        const int lane = threadIdx.x & 63, leader = __builtin_ctzll(pm);
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(&qctl[0], (uint32_t)__popcll(pm));
+        base = __builtin_amdgcn_readlane(base, leader);
+        if (push) queue[base + lanes_below(pm)] = rec;
+    }
+}
+
+// A ray frame on every other schedule (MIRT_TRAV_TILE, brute force): each lane
+// traces its pixel's whole path, as render_kernel does (trace_path, with the
+// planes' slot), from the loaded ray. trace_path takes zero-component rays
+// itself, so nothing is deferred.
+template <bool FAST, class... PLANES>
+__global__ __launch_bounds__(256) void ray_path_kernel(DevScene sc, FrameConst f, const mirt_ray* __restrict__ rays,
+                                                       uint32_t* __restrict__ out, float* __restrict__ acc,
+                                                       PLANES... planes)
+{
+    __shared__ uint32_t cstack[kMaxDepth * 256];
+    __shared__ uint32_t wstack[kWideStack * kWideStride];
+    int x, r;
+    const bool alive = ray_tile_pixel(f, x, r);
+    const size_t i = alive ? (size_t)r * f.width + x : 0;
+    const Ray ray = load_ray(rays, i);
+    const int y = alive ? shard_row_to_y(f, r) : 0;
+    Counters cnt{0, 0, 0, 0, 0};
+    const uint32_t c = trace_path<FAST, false>(sc, ray, alive, f.depth, f.use_bvh != 0,
+                                               pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r)), cnt,
+                                               cstack + threadIdx.x, 256, wstack + threadIdx.x, PlaneSlot{planes, i}...);
+    if (alive) store_pixel(f, out, acc, i, c);
+}
+
 // The bounce kernel's walks test the HNode slot boxes without
 // slab_cons_fast's margins (trace.h, BND): the boxes are grown by 2^-19
 // DevScene::o_bound at upload, and a bounce ray whose origin lies within that
@@ -1712,6 +1836,9 @@ struct mirt_ctx {
     size_t queue_cap = 0;
     bool lone_frame = false;    // mirt_render_frame's frame: the first bounces queued in tile order
     Planes planes;              // mirt_render_frame_planes*: the planes of the frame being enqueued
+    const mirt_ray* rays = nullptr;  // mirt_render_rays*: the camera rays of the frame being enqueued (device memory)
+    void* d_rays = nullptr;     // rays of the blocking form, copied from the host ahead of the frame
+    size_t rays_cap = 0;
     void* d_planes = nullptr;   // planes of the blocking / async forms, copied to the host behind the frame
     size_t planes_cap = 0;
     PrimaryCache pc;            // MIRT_OPT_PRIMARY_CACHE: the camera rays' hits of a still camera
@@ -2033,6 +2160,34 @@ void launch_primary(int blocks, hipStream_t s, const DevScene& sc, const FrameCo
         primary_kernel<FAST, ORD, BND><<<blocks, 256, 0, s>>>(sc, f, d_out, d_acc, dfr, queue, qctl, octants);
 }
 
+// The kernels of a ray frame (c->rays), with the planes' stores if it has any.
+void launch_ray_primary(bool fast, int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f,
+                        const mirt_ray* rays, uint32_t* d_out, float* d_acc, BounceRec* queue, uint32_t* qctl,
+                        const Planes& pl)
+{
+    if (fast && has_planes(pl))
+        ray_primary_kernel<true><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, queue, qctl, pl);
+    else if (fast)
+        ray_primary_kernel<true><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, queue, qctl);
+    else if (has_planes(pl))
+        ray_primary_kernel<false><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, queue, qctl, pl);
+    else
+        ray_primary_kernel<false><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, queue, qctl);
+}
+
+void launch_ray_path(bool fast, int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f,
+                     const mirt_ray* rays, uint32_t* d_out, float* d_acc, const Planes& pl)
+{
+    if (fast && has_planes(pl))
+        ray_path_kernel<true><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, pl);
+    else if (fast)
+        ray_path_kernel<true><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc);
+    else if (has_planes(pl))
+        ray_path_kernel<false><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc, pl);
+    else
+        ray_path_kernel<false><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc);
+}
+
 template <bool COUNT>
 void dispatch_render(bool fast, const DevScene& sc, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s,
                      int blocks, int bw, mirt_counts* d_counts, uint32_t* d_ws, Deferred dfr, const Planes& pl)
@@ -2095,7 +2250,8 @@ bool camera_bounded(const mirt_ctx* c, const FrameConst& f)
 // MIRT_OPT_PRIMARY_CACHE: the frame being enqueued is a bypass, a hit or a
 // fill, decided here on the host. diag: a counting or diagnostic
 // launch. Eligible is exactly the frame for which launch_render_body picks
-// primary_kernel<true, true, *>, without jitter and without planes; the
+// primary_kernel<true, true, *>, without jitter, without planes and with the
+// pinhole's rays (a ray frame, c->rays, has no camera to key a cache by); the
 // reasons are looked for in the order of the enum. A fill whose slab outgrows
 // the allocation waits for the frames that may still read it, then grows it
 // (the rule of d_planes): no allocation on a hit or a same-size fill.
@@ -2107,7 +2263,7 @@ int pc_classify(mirt_ctx* c, const FrameConst& f, bool diag, PrimaryUse* use)
     const bool packet = c->trav == kTravWavefront && f.use_bvh && f.depth >= 1 && !diag && c->fast_slab &&
                         dev_scene(c).ordered && f.num_rows > 0 && f.width > 0;
     const int why = !packet ? MIRT_PCACHE_SCHEDULE : f.jitter ? MIRT_PCACHE_JITTER
-                    : has_planes(c->planes) ? MIRT_PCACHE_PLANES : 0;
+                    : has_planes(c->planes) ? MIRT_PCACHE_PLANES : c->rays ? MIRT_PCACHE_RAYS : 0;
     if (why) {
         pc.bypassed++;
         pc.last = MIRT_PCACHE_BYPASS;
@@ -2200,8 +2356,12 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
     const bool wavefront = c->trav == kTravWavefront && f.use_bvh && f.depth >= 2 && !d_counts;
     // depth 1 (camera rays and their shading only): the camera-packet kernel
     // alone, at its 8 waves per SIMD, where the tree admits the ordered walk
+    const mirt_ray* const rays = c->rays;   // a ray frame (mirt_render_rays*): never a counting launch
     const bool primary_only = c->trav == kTravWavefront && f.use_bvh && f.depth == 1 && !d_counts && c->fast_slab &&
-                              dev_scene(c).ordered;
+                              dev_scene(c).ordered && !rays;
+    // a ray frame on the wavefront schedule: ray_primary_kernel at every depth,
+    // alone below depth 2; on the others ray_path_kernel
+    const bool ray_primary = rays && c->trav == kTravWavefront && f.use_bvh;
     const int dbw = wavefront || primary_only ? 4 : bw;  // the wavefront kernels use 256-thread workgroups
     Deferred dfr{nullptr, nullptr, 0};
     c->phases_valid = wavefront;
@@ -2213,7 +2373,7 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
     }
     const DevScene sc = dev_scene(c);
     // the ordered packet walk takes zero-component camera rays itself
-    if (f.use_bvh && c->defer && !sc.ordered) {
+    if (f.use_bvh && c->defer && !sc.ordered && !rays) {
         const size_t pixels = (size_t)f.num_rows * f.width;
         int rc = ensure((void**)&c->d_defer, &c->defer_cap, 4 * (pixels + 1));
         if (rc) return rc;
@@ -2243,6 +2403,17 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
         return MIRT_OK;
     }
+    if (ray_primary && !wavefront) {
+        // depth 0 and 1: no bounce records (the queue is passed, never written)
+        int rc = ensure(&c->d_queue, &c->queue_cap, sizeof(BounceRec) + kQCtlBytes);
+        if (rc) return rc;
+        launch_ray_primary(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, rays, d_out, d_acc,
+                           (BounceRec*)((char*)c->d_queue + kQCtlBytes), (uint32_t*)c->d_queue, c->planes);
+        HIP_TRY(hipGetLastError());
+        if (int rc2 = fold()) return rc2;
+        if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
+        return MIRT_OK;
+    }
     if (wavefront) {
         const size_t pixels = (size_t)f.num_rows * f.width;
         int rc = ensure(&c->d_queue, &c->queue_cap, sizeof(BounceRec) * pixels + kQCtlBytes);
@@ -2252,14 +2423,16 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         HIP_TRY(hipMemsetAsync(qctl, 0, kQCtlBytes, s));
         // primary_kernel's packets: 8x8 pixel tiles, or 4x4 pixels x 4 frames
         // for an ordered walk over four frames or more
-        const int ptiles = c->fast_slab && sc.ordered && f.samples >= 4
+        const int ptiles = c->fast_slab && sc.ordered && f.samples >= 4 && !rays
                                ? ((f.width + 3) / 4) * ((f.shard_rows + 3) / 4) * ((f.samples + 3) / 4)
                                : tiles;
         const int pblocks = (ptiles + 3) / 4 + dfr.blocks;
         const int bblocks = c->bounce_blocks_opt ? c->bounce_blocks_opt : c->bounce_blocks;
         const size_t blds = bounce_lds_bytes(f.depth);
         const int oq = octant_queue(c);
-        if (c->fast_slab && sc.ordered && camera_bounded(c, f))
+        if (rays)
+            launch_ray_primary(c->fast_slab != 0, pblocks, s, sc, f, rays, d_out, d_acc, queue, qctl, c->planes);
+        else if (c->fast_slab && sc.ordered && camera_bounded(c, f))
             launch_primary<true, true, true>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes, pcu);
         else if (c->fast_slab && sc.ordered)
             launch_primary<true, true, false>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes, pcu);
@@ -2287,7 +2460,9 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
         return MIRT_OK;
     }
-    if (d_counts)
+    if (rays)
+        launch_ray_path(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, rays, d_out, d_acc, c->planes);
+    else if (d_counts)
         dispatch_render<true>(true, sc, f, d_out, d_acc, s, blocks, bw, d_counts, d_wave_stats, dfr, c->planes);
     else
         dispatch_render<false>(c->fast_slab != 0, sc, f, d_out, d_acc, s, blocks, bw, nullptr, nullptr, dfr, c->planes);
@@ -2406,7 +2581,7 @@ void mirt_destroy(mirt_ctx* c)
     mirt::build_state_free(c->build);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
-                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->pc.d})
+                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d})
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2576,21 +2751,28 @@ try {
     return MIRT_E_NOMEM;
 }
 
-int mirt_render_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
-                             float* d_acc, void* stream)
+// mirt_render_frame_device, under the name `fn` of the entry point it serves.
+static int render_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
+                               float* d_acc, void* stream, const char* fn)
 {
-    if (!ctx_ok(c, true, "mirt_render_frame_device")) return MIRT_E_NOSCENE;
+    if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
     if (!cam || !frame_desc_valid(fd) || !d_out || (fd->accumulate && !d_acc)) {
-        set_error("mirt_render_frame_device: invalid arguments");
+        set_error("%s: invalid arguments", fn);
         return MIRT_E_INVALID;
     }
     if (fd->use_bvh && scene_of(c)->num_nodes == 0) {
-        set_error("mirt_render_frame_device: use_bvh set but no tree uploaded");
+        set_error("%s: use_bvh set but no tree uploaded", fn);
         return MIRT_E_NOSCENE;
     }
     const FrameConst f = make_frame_const(cam, fd);
     c->frame_cam = *cam;
     return launch_render(c, f, d_out, d_acc, (hipStream_t)stream, false, nullptr);
+}
+
+int mirt_render_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
+                             float* d_acc, void* stream)
+{
+    return render_frame_device(c, cam, fd, d_out, d_acc, stream, "mirt_render_frame_device");
 }
 
 }  // extern "C"
@@ -2851,16 +3033,22 @@ static int enqueue_frame_to_host(mirt_ctx* c, const mirt_camera* cam, const mirt
 // The blocking call renders one frame with nothing after it on the ctx: its
 // first bounces go to the queue in tile order (lone_frame), which the
 // bounce pass walks 2-4% faster when no other frame shares the chip.
-int mirt_render_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out)
+static int render_frame_blocking(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out,
+                                 const char* fn)
 {
     if (c) c->lone_frame = true;
-    const int rc = enqueue_frame_to_host(c, cam, fd, out, c && c->zero_copy, "mirt_render_frame");
+    const int rc = enqueue_frame_to_host(c, cam, fd, out, c && c->zero_copy, fn);
     if (c) c->lone_frame = false;
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     // (an empty shard records no events: last_ms stays the last timed frame's)
     if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
+}
+
+int mirt_render_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out)
+{
+    return render_frame_blocking(c, cam, fd, out, "mirt_render_frame");
 }
 
 int mirt_render_frame_async(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, mirt_rgba8* out)
@@ -2946,6 +3134,63 @@ int mirt_render_frame_planes_async(mirt_ctx* c, const mirt_camera* cam, const mi
                                    const mirt_primary_planes* planes)
 {
     return render_frame_planes_host(c, cam, fd, out, planes, false, "mirt_render_frame_planes_async");
+}
+
+// ---- ray frames (caller-given camera rays)
+
+// What the ray forms check before the ctx is used and before any HIP call.
+static bool rays_args_ok(const mirt_ctx* c, const mirt_ray* rays, const mirt_frame_desc* fd,
+                         const mirt_primary_planes* pl, const char* fn)
+{
+    if (!c) {
+        set_error("%s: null context", fn);
+        return false;
+    }
+    if (!rays || !frame_desc_valid(fd) || fd->jitter ||
+        (pl && (!(pl->t || pl->sphere || pl->normal) || fd->max_depth < 1))) {
+        set_error("%s: invalid arguments", fn);
+        return false;
+    }
+    return true;
+}
+
+// A ray frame has no camera: FrameConst's camera fields are never read by its
+// kernels, nor by the bounce pass, the folds or the row map.
+static const mirt_camera kNoCamera{};
+
+int mirt_render_rays_device(mirt_ctx* c, const mirt_ray* d_rays, const mirt_frame_desc* fd, uint32_t* d_out,
+                            float* d_acc, const mirt_primary_planes* d_planes, void* stream)
+{
+    const char* fn = "mirt_render_rays_device";
+    if (!rays_args_ok(c, d_rays, fd, d_planes, fn)) return MIRT_E_INVALID;
+    c->rays = d_rays;
+    if (d_planes) c->planes = Planes{d_planes->t, d_planes->sphere, d_planes->normal};
+    const int rc = render_frame_device(c, &kNoCamera, fd, d_out, d_acc, stream, fn);
+    c->planes = Planes{};
+    c->rays = nullptr;
+    return rc;
+}
+
+int mirt_render_rays(mirt_ctx* c, const mirt_ray* rays, const mirt_frame_desc* fd, mirt_rgba8* out,
+                     const mirt_primary_planes* planes)
+{
+    const char* fn = "mirt_render_rays";
+    if (!rays_args_ok(c, rays, fd, planes, fn)) return MIRT_E_INVALID;
+    if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
+    if (!out) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    const size_t bytes = sizeof(mirt_ray) * (size_t)shard_row_count(fd) * fd->width * (fd->samples > 1 ? fd->samples : 1);
+    // the blocking call leaves nothing in flight that reads the buffer: it may grow at once
+    if (int rc = ensure(&c->d_rays, &c->rays_cap, bytes)) return rc;
+    if (bytes) HIP_TRY(hipMemcpyAsync(c->d_rays, rays, bytes, hipMemcpyHostToDevice, c->stream));
+    // (an empty shard launches nothing: its rays are not read, wherever they are)
+    c->rays = bytes ? (const mirt_ray*)c->d_rays : rays;
+    const int rc = planes ? render_frame_planes_host(c, &kNoCamera, fd, out, planes, true, fn)
+                          : render_frame_blocking(c, &kNoCamera, fd, out, fn);
+    c->rays = nullptr;
+    return rc;
 }
 
 int mirt_ctx_wait(mirt_ctx* c)

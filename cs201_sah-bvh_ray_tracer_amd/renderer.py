@@ -614,6 +614,40 @@ class Renderer:
         check(self.L.mirt_render_frame_planes_async(self.h, C.byref(cam), C.byref(fd), ptr(arr), C.byref(pl)),
               "mirt_render_frame_planes_async")
 
+    # ---- ray frames (the caller's camera rays)
+    def render_rays(self, rays, width, height, planes=None, **frame_desc_args):
+        """render_frame (frame_desc's keyword arguments) of caller-given camera
+        rays (mirt_render_rays): `rays` is an abi.RAY array of samples * rows *
+        width elements, indexed as the colour output and the planes are (slab j
+        = frame j's rays, rows in the shard's order), used as given. Returns
+        the (rows, width, 4) uint8 display after the last frame, or, with
+        `planes` (names as for render_frame_planes), (rgba, dict)."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        rays = np.ascontiguousarray(rays, abi.RAY)
+        if rays.size != max(fd.samples, 1) * n * width:
+            raise MirtError(f"render_rays: {rays.size} rays, the frame needs {max(fd.samples, 1) * n * width}")
+        out = np.zeros((n, width, 4), np.uint8)
+        bufs, pl = None, None
+        if planes is not None:
+            lead = (fd.samples, n, width) if fd.samples > 1 else (n, width)
+            self._planes_struct(dict.fromkeys(planes, 0), "render_rays")   # the names
+            bufs = {k: np.zeros(lead + self.PLANES[k][1], self.PLANES[k][0]) for k in planes}
+            pl = C.byref(self._planes_struct({k: b.ctypes.data for k, b in bufs.items()}, "render_rays"))
+        # (an empty array has no address worth passing, but NULL rays are an error: its own, unread, will do)
+        check(self.L.mirt_render_rays(self.h, C.c_void_p(rays.ctypes.data), C.byref(fd), ptr(out), pl),
+              "mirt_render_rays")
+        return out if planes is None else (out, bufs)
+
+    def render_rays_device(self, d_rays, fd, d_out, d_acc=None, d_planes=None, stream=None):
+        """Enqueue a ray frame on device memory (integer device pointers):
+        d_rays holds samples * rows * width 24-byte rays, read on `stream`;
+        d_planes maps "t" / "sphere" / "normal" to device pointers, or None."""
+        pl = C.byref(self._planes_struct(d_planes, "render_rays_device")) if d_planes is not None else None
+        check(self.L.mirt_render_rays_device(self.h, C.c_void_p(d_rays), C.byref(fd), C.c_void_p(d_out),
+                                             C.c_void_p(d_acc) if d_acc else None, pl, C.c_void_p(stream or 0)),
+              "mirt_render_rays_device")
+
     def share_accum(self, owner):
         """Use `owner`'s accumulation buffer (mirt_ctx_share_accum): the ctxs
         of one accumulating display loop with frames in flight; None: a

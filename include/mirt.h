@@ -588,6 +588,44 @@ int mirt_render_frame_planes_device(mirt_ctx *ctx, const mirt_camera *cam, const
 int mirt_render_frame_planes_async(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd, mirt_rgba8 *out,
                                    const mirt_primary_planes *planes);
 
+/* Ray frames: a frame whose camera rays the caller gives -- a thin lens, a
+   fisheye, an orthographic or stereo camera, a lens-distortion table, its own
+   anti-aliasing pattern. A ray frame is a frame in every respect (fd's
+   geometry, shard, row_block, lead_skip, samples, max_depth, use_bvh, seed,
+   sample, accumulate, frames; the ctx's buffers, mirt_ctx_share_accum chains
+   and the folds of samples > 1; every schedule of mirt_set_option) except that
+   pixel i's camera ray is rays[i]. `rays` is indexed exactly as the colour
+   output of the device form and as the planes are: `samples` slabs of
+   num_rows * width, element r * width + x in shard row order, slab j holding
+   frame j's rays (so the lens can be re-sampled per frame); indices are
+   computed in size_t. Rays are used as given -- direction not normalised, any
+   origin -- the contract of mirt_trace_rays. The pixel's RNG stream is the
+   frame's (seed, pixel y * width + x of image row y, sample + j), hence:
+     a ray frame fed mirt_camera_rays(fd) is mirt_render_frame(cam, fd) byte
+       for byte;
+     for any rays, an unsharded one-sample ray frame is mirt_trace_rays(rays,
+       width * height, max_depth, use_bvh, seed, sample), and a shard's row y
+       is mirt_trace_rays_at(..., pixel0 = y * width);
+     with planes, element i is the t, sphere and normal of
+       mirt_intersect_rays(rays)[i].
+   Checks, errors and accumulation are those of mirt_render_frame_device /
+   mirt_render_frame; in addition MIRT_E_INVALID, before any device call, for
+   a NULL ctx, NULL rays, an invalid fd, fd->jitter != 0 (the caller owns the
+   sample points), a planes struct without a member, or planes with
+   fd->max_depth < 1. An empty shard is MIRT_OK, launches nothing and reads and
+   writes nothing. On the default schedule (use_bvh) the camera pass walks one
+   ray per lane, as mirt_intersect_rays does, and hands the first bounces to the
+   bounce pass of a plain frame. With MIRT_OPT_PRIMARY_CACHE 1 a ray frame is a
+   BYPASS (reason MIRT_PCACHE_RAYS) and leaves a valid cache valid.
+   _device: rays in device memory (24-byte mirt_ray), read on `stream`; d_planes
+   may be NULL. The blocking form takes host pointers: the rays are copied to a
+   buffer the ctx keeps (grown like its other buffers), `out` receives the last
+   display as mirt_render_frame's does, planes may be NULL. */
+int mirt_render_rays_device(mirt_ctx *ctx, const mirt_ray *d_rays, const mirt_frame_desc *fd, uint32_t *d_out,
+                            float *d_accum, const mirt_primary_planes *d_planes, void *stream);
+int mirt_render_rays(mirt_ctx *ctx, const mirt_ray *rays, const mirt_frame_desc *fd, mirt_rgba8 *out,
+                     const mirt_primary_planes *planes);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
@@ -946,7 +984,7 @@ int mirt_get_option(mirt_ctx *ctx, int option);
        (MIRT_TRAV_TILE, brute force, a tree without ordered walks,
        MIRT_OPT_FAST_SLAB / _PRUNE / _ORDERED 0, depth 0, mirt_count_frame,
        mirt_wave_stats, mirt_bounce_stats); JITTER -- fd->jitter; PLANES -- a
-       mirt_render_frame_planes* frame.
+       mirt_render_frame_planes* frame; RAYS -- a mirt_render_rays* frame.
      The key of every other frame, compared bitwise: what its camera rays and
        its pixel -> row map are computed from (the camera as the frame sees it:
        position, forward, and the horizontal and vertical spans; aspect, width,
@@ -969,7 +1007,8 @@ int mirt_get_option(mirt_ctx *ctx, int option);
 enum { MIRT_PCACHE_BYPASS = 0, MIRT_PCACHE_FILL = 1, MIRT_PCACHE_HIT = 2 };
 enum { MIRT_PCACHE_EMPTY = 1, MIRT_PCACHE_SCENE = 2, MIRT_PCACHE_CAMERA = 3, MIRT_PCACHE_GEOMETRY = 4,
        MIRT_PCACHE_OFF = 5, /* the option is 0 (what mirt_primary_cache_stats_get then reports) */
-       MIRT_PCACHE_SCHEDULE = 6, MIRT_PCACHE_JITTER = 7, MIRT_PCACHE_PLANES = 8 };
+       MIRT_PCACHE_SCHEDULE = 6, MIRT_PCACHE_JITTER = 7, MIRT_PCACHE_PLANES = 8,
+       MIRT_PCACHE_RAYS = 9 /* a ray frame (mirt_render_rays*): no camera to key by */ };
 typedef struct mirt_primary_cache_stats {
     uint64_t hits, fills, bypassed;   /* frames classified since the option was last set to 1 */
     uint64_t scene_id;                /* of the key; 0 when not valid */
