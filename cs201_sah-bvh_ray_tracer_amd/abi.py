@@ -101,6 +101,11 @@ class PrimaryPlanes(C.Structure):
     _fields_ = [("t", C.c_void_p), ("sphere", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class Lens(C.Structure):
+    """mirt_lens: a thin lens (aperture 0 = the pinhole)"""
+    _fields_ = [("aperture", C.c_float), ("focus", C.c_float)]
+
+
 class PrimaryCacheStats(C.Structure):
     """mirt_primary_cache_stats"""
     _fields_ = [("hits", C.c_uint64), ("fills", C.c_uint64), ("bypassed", C.c_uint64), ("scene_id", C.c_uint64),
@@ -240,6 +245,10 @@ SIGNATURES = [
     ("mirt_render_frame_planes_async", I, [P, P, P, P, P]),
     ("mirt_render_rays_device", I, [P, P, P, P, P, P, P]),
     ("mirt_render_rays", I, [P, P, P, P, P]),
+    ("mirt_lens_rays", I, [P, P, P, P, P]),
+    ("mirt_render_lens_frame", I, [P, P, P, P, P, P]),
+    ("mirt_render_lens_frame_device", I, [P, P, P, P, P, P, P, P]),
+    ("mirt_render_lens_frame_async", I, [P, P, P, P, P, P]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),
@@ -308,6 +317,7 @@ SIGNATURES = [
     ("mirt_multi_render_frame", I, [P, P, P, P]),
     ("mirt_multi_render_frame_async", I, [P, P, P, P]),
     ("mirt_multi_render_frames_async", I, [P, P, P, I, I, C.POINTER(P)]),
+    ("mirt_multi_render_lens_frames_async", I, [P, P, P, P, I, I, C.POINTER(P)]),
     ("mirt_multi_wait", I, [P]),
     ("mirt_multi_get_stats", I, [P, P]),
     ("mirt_multi_read_gathered", I, [P, I, I, I, P, C.c_size_t]),
@@ -325,6 +335,9 @@ PCACHE_BYPASS, PCACHE_FILL, PCACHE_HIT = 0, 1, 2
 PCACHE_KIND = {PCACHE_BYPASS: "bypass", PCACHE_FILL: "fill", PCACHE_HIT: "hit"}
 PCACHE_REASON = {0: "", 1: "EMPTY", 2: "SCENE", 3: "CAMERA", 4: "GEOMETRY", 5: "OFF", 6: "SCHEDULE", 7: "JITTER",
                  8: "PLANES", 9: "RAYS"}
+# MIRT_PCACHE_LENS, which mirt.h writes as MIRT_PCACHE_RAYS + 1 (PCACHE_REASON holds the reasons written as literals)
+PCACHE_LENS = 10
+PCACHE_REASON_NAME = {**PCACHE_REASON, PCACHE_LENS: "LENS"}
 BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4

@@ -32,8 +32,10 @@ int validate_flat(const mirt_node* nd, int nn, int num_spheres, int sphere_lo, c
 // FRESH frames (main.c:358-374 each), left raw in their slabs, the last one
 // folded into the accumulation buffer as a fresh frame; otherwise they fold in
 // order (a frame of several samples / the accumulating display loop).
+// lens (valid, aperture > 0): the frame is a lens frame (mirt_render_lens_frame*).
 int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
-                         uint32_t** d_display, const char* fn, bool independent = false);
+                         uint32_t** d_display, const char* fn, bool independent = false,
+                         const mirt_lens* lens = nullptr);
 int ctx_device(const mirt_ctx* c);
 int ctx_build_finish(const mirt_ctx* c);  // MIRT_OPT_BUILD_FINISH as stored: 0 off, 1 automatic, 2..64 = F
 // bvh_device.hip: the device builder's scratch and statistics, kept on the ctx

@@ -32,6 +32,7 @@
 
 #include "../../include/mirt_multi.h"
 #include "internal.h"
+#include "lens.h"
 #include "shard.h"
 
 using namespace mirt;
@@ -142,6 +143,8 @@ struct Launch {
     ShardSrc sr{};                  // rows of every shard (p[] filled by rank 0)
     size_t shard_stride = 0, frame_elems = 0;
     std::vector<mirt_rgba8*> dst;   // frame j's host destination (page-locked: the caller's or the staging)
+    bool has_lens = false;          // mirt_multi_render_lens_frames_async with aperture > 0: lens frames
+    mirt_lens lens{};
 };
 
 // One launch in flight: a context per rank, the gather buffer and the frames
@@ -529,7 +532,8 @@ int issue_rank_body(mirt_multi* m, Lane& L, int r)
         if (int g = grow(m->dev[r], &L.slab[r], &L.slab_cap[r], need)) return g;
         out = L.slab[r];
     }
-    int rc = enqueue_frame_device(c, &J.cam, &sd, out, &disp, "mirt_multi_render_frames_async", J.nframes > 1);
+    int rc = enqueue_frame_device(c, &J.cam, &sd, out, &disp, "mirt_multi_render_frames_async", J.nframes > 1,
+                                  J.has_lens ? &J.lens : nullptr);
     if (J.flags & MIRT_MULTI_FULL_GRID) (void)mirt_set_option(c, MIRT_OPT_BOUNCE_BLOCKS, keep);
     if (rc) return rc;
     uint32_t* src = disp - (size_t)(J.nframes - 1) * elems;   // spp == 1 when nframes > 1: slab j = frame j
@@ -767,11 +771,13 @@ void rank_thread_main(mirt_multi* m, int r, RankThread* wp)
 
 // Launch on lane li: prepared here, issued by every rank (its own thread
 // when n > 1).
-int enqueue(mirt_multi* m, int li, const mirt_camera* cam, const mirt_frame_desc* fd, int nframes, int flags,
-            mirt_rgba8* const* outs)
+int enqueue(mirt_multi* m, int li, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+            int nframes, int flags, mirt_rgba8* const* outs)
 {
     Lane& L = m->lanes[li];
     if (int rc = prepare(m, L, cam, fd, nframes, flags, outs)) return rc;
+    L.job.has_lens = lens != nullptr;   // only the 8-byte struct travels to the ranks
+    if (lens) L.job.lens = *lens;
     L.seq++;
     L.err = MIRT_OK;
     L.issued->store(0, std::memory_order_relaxed);
@@ -1273,11 +1279,11 @@ try {
     return MIRT_E_NOMEM;
 }
 
-int mirt_multi_render_frames_async(mirt_multi* m, const mirt_camera* cam, const mirt_frame_desc* fd, int nframes,
-                                   int flags, mirt_rgba8* const* outs)
-try {
-    const char* fn = "mirt_multi_render_frames_async";
-    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+// mirt_multi_render_frames_async under the name `fn`; lens (aperture > 0): lens frames.
+static int render_frames_async(mirt_multi* m, const mirt_camera* cam, const mirt_lens* lens,
+                               const mirt_frame_desc* fd, int nframes, int flags, mirt_rgba8* const* outs,
+                               const char* fn)
+{
     if (m->failed) return failed_status(m, fn);
     if (int rc = check_frame(m, cam, fd, nframes, outs, fn)) return rc;
     const int li = m->next;
@@ -1286,13 +1292,38 @@ try {
         if (int rc = wait_sibling_kernels(m, li)) return rc;
     // an error here (before any rank issued) leaves the lane and the rotation
     // as they were; the ranks' own issue errors come back from the lane's wait
-    if (int rc = enqueue(m, li, cam, fd, nframes, flags, outs)) return rc;
+    if (int rc = enqueue(m, li, cam, lens, fd, nframes, flags, outs)) return rc;
     m->next = (m->next + 1) % (int)m->lanes.size();
     m->last_lane = li;
     m->st_launches.fetch_add(1);
     return MIRT_OK;
+}
+
+int mirt_multi_render_frames_async(mirt_multi* m, const mirt_camera* cam, const mirt_frame_desc* fd, int nframes,
+                                   int flags, mirt_rgba8* const* outs)
+try {
+    const char* fn = "mirt_multi_render_frames_async";
+    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+    return render_frames_async(m, cam, nullptr, fd, nframes, flags, outs, fn);
 } catch (const std::bad_alloc&) {
     set_error("mirt_multi_render_frames_async: out of host memory");
+    return MIRT_E_NOMEM;
+}
+
+int mirt_multi_render_lens_frames_async(mirt_multi* m, const mirt_camera* cam, const mirt_lens* lens,
+                                        const mirt_frame_desc* fd, int nframes, int flags, mirt_rgba8* const* outs)
+try {
+    const char* fn = "mirt_multi_render_lens_frames_async";
+    if (!multi_ok(m, fn)) return MIRT_E_INVALID;
+    if (!cam || !fd || !lens_valid(lens)) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    if (lens->aperture == 0.0f)   // the pinhole, by definition: plain frames
+        return mirt_multi_render_frames_async(m, cam, fd, nframes, flags, outs);
+    return render_frames_async(m, cam, lens, fd, nframes, flags, outs, fn);
+} catch (const std::bad_alloc&) {
+    set_error("mirt_multi_render_lens_frames_async: out of host memory");
     return MIRT_E_NOMEM;
 }
 

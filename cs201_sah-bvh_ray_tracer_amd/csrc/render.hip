@@ -19,6 +19,7 @@
 
 #include "coop.h"
 #include "internal.h"
+#include "lens.h"
 #include "shard.h"
 #include "trace.h"
 
@@ -659,6 +660,119 @@ __global__ __launch_bounds__(256) void ray_path_kernel(DevScene sc, FrameConst f
                                                pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r)), cnt,
                                                cstack + threadIdx.x, 256, wstack + threadIdx.x, PlaneSlot{planes, i}...);
     if (alive) store_pixel(f, out, acc, i, c);
+}
+
+// ------------------------------------------------------------------------
+// Lens frames (mirt_render_lens_frame*): a ray frame whose rays the camera pass
+// computes itself -- each lane its pixel's thin-lens ray, from the pinhole ray
+// and the pixel's RNG contract stream (lens.h has the definition) -- so no ray
+// buffer exists anywhere. What follows the ray is the ray frame's, line for
+// line; the kernels are their own so that the plain and the ray kernels keep
+// their arguments and their code.
+
+// The lens ray of pixel (x, image row y) of RNG sample `sample` under `key`,
+// the pixel's own key: what mirt_lens_rays writes and both frame kernels trace.
+__device__ __forceinline__ Ray lens_camera_ray(const FrameConst& f, const LensConst& lc, int x, int y, uint32_t sample,
+                                               uint64_t key)
+{
+    const Ray pr = camera_ray(f, x, y, sample);
+    const float p[3] = {pr.ox, pr.oy, pr.oz}, d[3] = {pr.dx, pr.dy, pr.dz};
+    float o[3], n[3];
+    lens_ray(lc, key, p, d, o, n);
+    normalize3(n[0], n[1], n[2]);
+    return Ray{o[0], o[1], o[2], n[0], n[1], n[2]};
+}
+
+// The camera pass of a lens frame on the wavefront schedule: ray_primary_kernel
+// with the lane's ray computed in registers from (x, image row, row_sample).
+// The origins differ from lane to lane, so the walk is the per-lane one
+// (closest_hit<false>), not the pinhole's packets. Depth 0 stores black
+// without computing a ray.
+template <bool FAST, class... PLANES>
+__global__ __launch_bounds__(256) void lens_primary_kernel(DevScene sc, FrameConst f, LensConst lc,
+                                                           uint32_t* __restrict__ out, float* __restrict__ acc,
+                                                           BounceRec* __restrict__ queue, uint32_t* __restrict__ qctl,
+                                                           PLANES... planes)
+{
+    __shared__ uint32_t wstack[kWideStack * kWideStride];
+    int x, r;
+    const bool alive = ray_tile_pixel(f, x, r);
+    const size_t i = alive ? (size_t)r * f.width + x : 0;
+    if (f.depth < 1) {
+        if (alive) store_pixel(f, out, acc, i, 255u << 24);
+        return;
+    }
+    if (!alive) x = r = 0;   // a dead lane computes pixel 0's ray and walks nothing
+    const int y = shard_row_to_y(f, r);
+    const uint64_t key = pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r));
+    const Ray ray = lens_camera_ray(f, lc, x, y, row_sample(f, r), key);
+    Counters cnt{0, 0, 0, 0, 0};
+    float t;
+    int s;
+    closest_hit<false, FAST, false>(sc, ray, alive, t, s, cnt, wstack + threadIdx.x);
+    if constexpr (sizeof...(PLANES) > 0) {
+        if (alive) (store_planes(planes, i, sc, ray, t, s), ...);
+    }
+    bool push = false;
+    BounceRec rec;
+    if (alive) {
+        if (s < 0) {
+            store_pixel(f, out, acc, i, sky_rgba(ray.dy));      // renderer.c:65-70
+        } else if (f.depth < 2) {
+            store_pixel(f, out, acc, i, blend_rgba(sc.color[s], 255u << 24));
+        } else {
+            const float4 g = sc.geo[s];
+            float p[3], n[3];
+            hit_point_normal(ray, t, g, p, n);
+            uint32_t k = 0;
+            float bx, by, bz;
+            hemisphere(key, k, n, bx, by, bz);
+            rec = BounceRec{p[0], p[1], p[2], bx, by, bz, (uint32_t)i, k, sc.color[s], 0u};
+            push = true;
+        }
+    }
+    const uint64_t pm = __ballot(push);
+    if (pm) {
+        const int lane = threadIdx.x & 63, leader = __builtin_ctzll(pm);
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(&qctl[0], (uint32_t)__popcll(pm));
+        base = __builtin_amdgcn_readlane(base, leader);
+        if (push) queue[base + lanes_below(pm)] = rec;
+    }
+}
+
+// A lens frame on every other schedule (MIRT_TRAV_TILE, brute force, the exact
+// slab, unordered trees): ray_path_kernel with the computed ray.
+template <bool FAST, class... PLANES>
+__global__ __launch_bounds__(256) void lens_path_kernel(DevScene sc, FrameConst f, LensConst lc,
+                                                        uint32_t* __restrict__ out, float* __restrict__ acc,
+                                                        PLANES... planes)
+{
+    __shared__ uint32_t cstack[kMaxDepth * 256];
+    __shared__ uint32_t wstack[kWideStack * kWideStride];
+    int x, r;
+    const bool alive = ray_tile_pixel(f, x, r);
+    const size_t i = alive ? (size_t)r * f.width + x : 0;
+    if (!alive) x = r = 0;
+    const int y = shard_row_to_y(f, r);
+    const uint64_t key = pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r));
+    const Ray ray = lens_camera_ray(f, lc, x, y, row_sample(f, r), key);
+    Counters cnt{0, 0, 0, 0, 0};
+    const uint32_t c = trace_path<FAST, false>(sc, ray, alive, f.depth, f.use_bvh != 0, key, cnt, cstack + threadIdx.x,
+                                               256, wstack + threadIdx.x, PlaneSlot{planes, i}...);
+    if (alive) store_pixel(f, out, acc, i, c);
+}
+
+// mirt_lens_rays: the rays a lens frame traces, indexed as its colour output.
+__global__ void lens_rays_kernel(FrameConst f, LensConst lc, mirt_ray* __restrict__ out)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y;
+    if (x >= f.width || r >= f.num_rows) return;
+    const int y = shard_row_to_y(f, r);
+    const Ray ray = lens_camera_ray(f, lc, x, y, row_sample(f, r),
+                                    pixel_key(f.seed, (uint32_t)(y * f.width + x), row_sample(f, r)));
+    out[(size_t)r * f.width + x] = {{ray.ox, ray.oy, ray.oz}, {ray.dx, ray.dy, ray.dz}};
 }
 
 // The bounce kernel's walks test the HNode slot boxes without
@@ -1839,6 +1953,7 @@ struct mirt_ctx {
     const mirt_ray* rays = nullptr;  // mirt_render_rays*: the camera rays of the frame being enqueued (device memory)
     void* d_rays = nullptr;     // rays of the blocking form, copied from the host ahead of the frame
     size_t rays_cap = 0;
+    const LensConst* lens = nullptr;  // mirt_render_lens_frame*: the lens of the frame being enqueued (aperture > 0)
     void* d_planes = nullptr;   // planes of the blocking / async forms, copied to the host behind the frame
     size_t planes_cap = 0;
     PrimaryCache pc;            // MIRT_OPT_PRIMARY_CACHE: the camera rays' hits of a still camera
@@ -2188,6 +2303,34 @@ void launch_ray_path(bool fast, int blocks, hipStream_t s, const DevScene& sc, c
         ray_path_kernel<false><<<blocks, 256, 0, s>>>(sc, f, rays, d_out, d_acc);
 }
 
+// The kernels of a lens frame (c->lens), with the planes' stores if it has any.
+void launch_lens_primary(bool fast, int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f,
+                         const LensConst& lc, uint32_t* d_out, float* d_acc, BounceRec* queue, uint32_t* qctl,
+                         const Planes& pl)
+{
+    if (fast && has_planes(pl))
+        lens_primary_kernel<true><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, queue, qctl, pl);
+    else if (fast)
+        lens_primary_kernel<true><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, queue, qctl);
+    else if (has_planes(pl))
+        lens_primary_kernel<false><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, queue, qctl, pl);
+    else
+        lens_primary_kernel<false><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, queue, qctl);
+}
+
+void launch_lens_path(bool fast, int blocks, hipStream_t s, const DevScene& sc, const FrameConst& f,
+                      const LensConst& lc, uint32_t* d_out, float* d_acc, const Planes& pl)
+{
+    if (fast && has_planes(pl))
+        lens_path_kernel<true><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, pl);
+    else if (fast)
+        lens_path_kernel<true><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc);
+    else if (has_planes(pl))
+        lens_path_kernel<false><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc, pl);
+    else
+        lens_path_kernel<false><<<blocks, 256, 0, s>>>(sc, f, lc, d_out, d_acc);
+}
+
 template <bool COUNT>
 void dispatch_render(bool fast, const DevScene& sc, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s,
                      int blocks, int bw, mirt_counts* d_counts, uint32_t* d_ws, Deferred dfr, const Planes& pl)
@@ -2251,7 +2394,8 @@ bool camera_bounded(const mirt_ctx* c, const FrameConst& f)
 // fill, decided here on the host. diag: a counting or diagnostic
 // launch. Eligible is exactly the frame for which launch_render_body picks
 // primary_kernel<true, true, *>, without jitter, without planes and with the
-// pinhole's rays (a ray frame, c->rays, has no camera to key a cache by); the
+// pinhole's rays (a ray frame, c->rays, has no camera to key a cache by, and a
+// lens frame, c->lens, draws other rays every sample); the
 // reasons are looked for in the order of the enum. A fill whose slab outgrows
 // the allocation waits for the frames that may still read it, then grows it
 // (the rule of d_planes): no allocation on a hit or a same-size fill.
@@ -2263,7 +2407,8 @@ int pc_classify(mirt_ctx* c, const FrameConst& f, bool diag, PrimaryUse* use)
     const bool packet = c->trav == kTravWavefront && f.use_bvh && f.depth >= 1 && !diag && c->fast_slab &&
                         dev_scene(c).ordered && f.num_rows > 0 && f.width > 0;
     const int why = !packet ? MIRT_PCACHE_SCHEDULE : f.jitter ? MIRT_PCACHE_JITTER
-                    : has_planes(c->planes) ? MIRT_PCACHE_PLANES : c->rays ? MIRT_PCACHE_RAYS : 0;
+                    : has_planes(c->planes) ? MIRT_PCACHE_PLANES : c->rays ? MIRT_PCACHE_RAYS
+                    : c->lens ? MIRT_PCACHE_LENS : 0;
     if (why) {
         pc.bypassed++;
         pc.last = MIRT_PCACHE_BYPASS;
@@ -2357,11 +2502,14 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
     // depth 1 (camera rays and their shading only): the camera-packet kernel
     // alone, at its 8 waves per SIMD, where the tree admits the ordered walk
     const mirt_ray* const rays = c->rays;   // a ray frame (mirt_render_rays*): never a counting launch
+    // a lens frame (mirt_render_lens_frame*) takes the ray frame's branches with its own kernels
+    const LensConst* const lens = rays ? nullptr : c->lens;
+    const bool given = rays || lens;
     const bool primary_only = c->trav == kTravWavefront && f.use_bvh && f.depth == 1 && !d_counts && c->fast_slab &&
-                              dev_scene(c).ordered && !rays;
+                              dev_scene(c).ordered && !given;
     // a ray frame on the wavefront schedule: ray_primary_kernel at every depth,
     // alone below depth 2; on the others ray_path_kernel
-    const bool ray_primary = rays && c->trav == kTravWavefront && f.use_bvh;
+    const bool ray_primary = given && c->trav == kTravWavefront && f.use_bvh;
     const int dbw = wavefront || primary_only ? 4 : bw;  // the wavefront kernels use 256-thread workgroups
     Deferred dfr{nullptr, nullptr, 0};
     c->phases_valid = wavefront;
@@ -2373,7 +2521,7 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
     }
     const DevScene sc = dev_scene(c);
     // the ordered packet walk takes zero-component camera rays itself
-    if (f.use_bvh && c->defer && !sc.ordered && !rays) {
+    if (f.use_bvh && c->defer && !sc.ordered && !given) {
         const size_t pixels = (size_t)f.num_rows * f.width;
         int rc = ensure((void**)&c->d_defer, &c->defer_cap, 4 * (pixels + 1));
         if (rc) return rc;
@@ -2407,8 +2555,12 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         // depth 0 and 1: no bounce records (the queue is passed, never written)
         int rc = ensure(&c->d_queue, &c->queue_cap, sizeof(BounceRec) + kQCtlBytes);
         if (rc) return rc;
-        launch_ray_primary(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, rays, d_out, d_acc,
-                           (BounceRec*)((char*)c->d_queue + kQCtlBytes), (uint32_t*)c->d_queue, c->planes);
+        if (lens)
+            launch_lens_primary(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, *lens, d_out, d_acc,
+                                (BounceRec*)((char*)c->d_queue + kQCtlBytes), (uint32_t*)c->d_queue, c->planes);
+        else
+            launch_ray_primary(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, rays, d_out, d_acc,
+                               (BounceRec*)((char*)c->d_queue + kQCtlBytes), (uint32_t*)c->d_queue, c->planes);
         HIP_TRY(hipGetLastError());
         if (int rc2 = fold()) return rc2;
         if (timed) HIP_TRY(hipEventRecord(c->ev1, s));
@@ -2423,7 +2575,7 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         HIP_TRY(hipMemsetAsync(qctl, 0, kQCtlBytes, s));
         // primary_kernel's packets: 8x8 pixel tiles, or 4x4 pixels x 4 frames
         // for an ordered walk over four frames or more
-        const int ptiles = c->fast_slab && sc.ordered && f.samples >= 4 && !rays
+        const int ptiles = c->fast_slab && sc.ordered && f.samples >= 4 && !given
                                ? ((f.width + 3) / 4) * ((f.shard_rows + 3) / 4) * ((f.samples + 3) / 4)
                                : tiles;
         const int pblocks = (ptiles + 3) / 4 + dfr.blocks;
@@ -2432,6 +2584,8 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const int oq = octant_queue(c);
         if (rays)
             launch_ray_primary(c->fast_slab != 0, pblocks, s, sc, f, rays, d_out, d_acc, queue, qctl, c->planes);
+        else if (lens)
+            launch_lens_primary(c->fast_slab != 0, pblocks, s, sc, f, *lens, d_out, d_acc, queue, qctl, c->planes);
         else if (c->fast_slab && sc.ordered && camera_bounded(c, f))
             launch_primary<true, true, true>(pblocks, s, sc, f, d_out, d_acc, dfr, queue, qctl, oq, c->planes, pcu);
         else if (c->fast_slab && sc.ordered)
@@ -2462,6 +2616,8 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
     }
     if (rays)
         launch_ray_path(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, rays, d_out, d_acc, c->planes);
+    else if (lens)
+        launch_lens_path(c->fast_slab != 0, (tiles + 3) / 4, s, sc, f, *lens, d_out, d_acc, c->planes);
     else if (d_counts)
         dispatch_render<true>(true, sc, f, d_out, d_acc, s, blocks, bw, d_counts, d_wave_stats, dfr, c->planes);
     else
@@ -2870,9 +3026,15 @@ int enqueue_host_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_des
 
 namespace mirt {
 int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd, uint32_t* d_out,
-                         uint32_t** d_display, const char* fn, bool independent)
+                         uint32_t** d_display, const char* fn, bool independent, const mirt_lens* lens)
 {
-    return enqueue_frame(c, cam, fd, d_out, d_display, fn, independent);
+    if (!c || !cam || !lens || !lens_valid(lens) || lens->aperture == 0.0f)   // a plain frame (enqueue_frame checks c, cam)
+        return enqueue_frame(c, cam, fd, d_out, d_display, fn, independent);
+    const LensConst lc = lens_const(cam, lens);
+    c->lens = &lc;
+    const int rc = enqueue_frame(c, cam, fd, d_out, d_display, fn, independent);
+    c->lens = nullptr;
+    return rc;
 }
 int ctx_device(const mirt_ctx* c) { return c->device; }
 int ctx_build_finish(const mirt_ctx* c) { return c->build_finish; }
@@ -3191,6 +3353,98 @@ int mirt_render_rays(mirt_ctx* c, const mirt_ray* rays, const mirt_frame_desc* f
                           : render_frame_blocking(c, &kNoCamera, fd, out, fn);
     c->rays = nullptr;
     return rc;
+}
+
+// ---- lens frames (a thin lens computed in the frame's own camera pass)
+
+static_assert(MIRT_PCACHE_LENS == 10, "mirt.h: the reasons' values are ABI");
+
+// What the lens forms check before the ctx is used and before any HIP call.
+static bool lens_args_ok(const mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                         const mirt_primary_planes* pl, const char* fn)
+{
+    if (!c) {
+        set_error("%s: null context", fn);
+        return false;
+    }
+    if (!cam || !lens_valid(lens) || !frame_desc_valid(fd) ||
+        (pl && (!(pl->t || pl->sphere || pl->normal) || fd->max_depth < 1))) {
+        set_error("%s: invalid arguments", fn);
+        return false;
+    }
+    return true;
+}
+
+int mirt_render_lens_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                                  uint32_t* d_out, float* d_acc, const mirt_primary_planes* d_planes, void* stream)
+{
+    const char* fn = "mirt_render_lens_frame_device";
+    if (!lens_args_ok(c, cam, lens, fd, d_planes, fn)) return MIRT_E_INVALID;
+    if (lens->aperture == 0.0f)   // the pinhole, by definition: the plain frame
+        return d_planes ? mirt_render_frame_planes_device(c, cam, fd, d_out, d_acc, d_planes, stream)
+                        : mirt_render_frame_device(c, cam, fd, d_out, d_acc, stream);
+    const LensConst lc = lens_const(cam, lens);
+    c->lens = &lc;
+    if (d_planes) c->planes = Planes{d_planes->t, d_planes->sphere, d_planes->normal};
+    const int rc = render_frame_device(c, cam, fd, d_out, d_acc, stream, fn);
+    c->planes = Planes{};
+    c->lens = nullptr;
+    return rc;
+}
+
+int mirt_render_lens_frame(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                           mirt_rgba8* out, const mirt_primary_planes* planes)
+{
+    const char* fn = "mirt_render_lens_frame";
+    if (!lens_args_ok(c, cam, lens, fd, planes, fn)) return MIRT_E_INVALID;
+    if (lens->aperture == 0.0f)
+        return planes ? mirt_render_frame_planes(c, cam, fd, out, planes) : mirt_render_frame(c, cam, fd, out);
+    const LensConst lc = lens_const(cam, lens);
+    c->lens = &lc;
+    const int rc = planes ? render_frame_planes_host(c, cam, fd, out, planes, true, fn)
+                          : render_frame_blocking(c, cam, fd, out, fn);
+    c->lens = nullptr;
+    return rc;
+}
+
+int mirt_render_lens_frame_async(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                                 mirt_rgba8* out, const mirt_primary_planes* planes)
+{
+    const char* fn = "mirt_render_lens_frame_async";
+    if (!lens_args_ok(c, cam, lens, fd, planes, fn)) return MIRT_E_INVALID;
+    if (lens->aperture == 0.0f)
+        return planes ? mirt_render_frame_planes_async(c, cam, fd, out, planes)
+                      : mirt_render_frame_async(c, cam, fd, out);
+    const LensConst lc = lens_const(cam, lens);
+    c->lens = &lc;   // read while the frame is enqueued: the kernels take the struct by value
+    const int rc = planes ? render_frame_planes_host(c, cam, fd, out, planes, false, fn)
+                          : enqueue_frame_to_host(c, cam, fd, out, c->zero_copy == 2, fn);
+    c->lens = nullptr;
+    return rc;
+}
+
+int mirt_lens_rays(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                   mirt_ray* out)
+{
+    const char* fn = "mirt_lens_rays";
+    if (!lens_args_ok(c, cam, lens, fd, nullptr, fn)) return MIRT_E_INVALID;
+    if (!out) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    if (lens->aperture == 0.0f) return mirt_camera_rays(c, cam, fd, out);
+    if (!ctx_ok(c, false, fn)) return MIRT_E_INVALID;
+    const FrameConst f = make_frame_const(cam, fd);
+    const LensConst lc = lens_const(cam, lens);
+    const size_t bytes = (size_t)f.num_rows * f.width * sizeof(mirt_ray);
+    if (int rc = ensure(&c->d_res, &c->res_cap, bytes + 4)) return rc;
+    if (f.num_rows > 0) {
+        lens_rays_kernel<<<dim3((f.width + 255) / 256, f.num_rows), 256, 0, c->stream>>>(f, lc, (mirt_ray*)c->d_res);
+        HIP_TRY(hipGetLastError());
+    }
+    if (bytes) HIP_TRY(hipMemcpyAsync(out, c->d_res, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
 }
 
 int mirt_ctx_wait(mirt_ctx* c)

@@ -45,4 +45,8 @@ MIRT_HD int draw(uint64_t key, uint32_t k)
 // bounce sampling (k = 0, 1, ...; a few dozen per pixel) never reaches.
 constexpr uint32_t kJitterDrawX = 0x7ffffff0u, kJitterDrawY = 0x7ffffff1u;
 
+// Lens frames (lens.h): the lens point's rejection sampling draws at
+// kLensDraw0 .. kLensDraw0 + 31 (16 tries of two), below the jitter's.
+constexpr uint32_t kLensDraw0 = 0x7fffff00u;
+
 }  // namespace mirt

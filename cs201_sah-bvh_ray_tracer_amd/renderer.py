@@ -282,7 +282,7 @@ def primary_cache_stats(handle):
     check(load().mirt_primary_cache_stats_get(handle, C.byref(st)), "mirt_primary_cache_stats_get")
     out = _fields(st)
     out["last"] = abi.PCACHE_KIND[st.last]
-    out["reason"] = abi.PCACHE_REASON[st.reason]
+    out["reason"] = abi.PCACHE_REASON_NAME[st.reason]
     return out
 
 
@@ -647,6 +647,72 @@ class Renderer:
         check(self.L.mirt_render_rays_device(self.h, C.c_void_p(d_rays), C.byref(fd), C.c_void_p(d_out),
                                              C.c_void_p(d_acc) if d_acc else None, pl, C.c_void_p(stream or 0)),
               "mirt_render_rays_device")
+
+    # ---- lens frames (a thin lens computed in the frame's own camera pass)
+    @staticmethod
+    def _lens(lens):
+        """abi.Lens from an abi.Lens or an (aperture, focus) pair."""
+        return lens if isinstance(lens, abi.Lens) else abi.Lens(*lens)
+
+    def lens_rays(self, cam, lens, width, height, **frame_desc_args):
+        """The rays a lens frame of these arguments traces (mirt_lens_rays): an
+        abi.RAY array (rows, width), or (samples, rows, width) with samples > 1,
+        indexed as the colour output (slab j = RNG sample sample + j)."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        out = np.zeros((fd.samples, n, width) if fd.samples > 1 else (n, width), abi.RAY)
+        check(self.L.mirt_lens_rays(self.h, C.byref(cam), C.byref(self._lens(lens)), C.byref(fd),
+                                    C.c_void_p(out.ctypes.data)), "mirt_lens_rays")
+        return out
+
+    def render_lens_frame(self, cam, lens, width, height, planes=None, **frame_desc_args):
+        """render_frame (frame_desc's keyword arguments: samples, accumulate,
+        shard, num_shards, ...) through the thin lens `lens` (an abi.Lens or
+        (aperture, focus); mirt_render_lens_frame). Returns the (rows, width, 4)
+        uint8 display after the last frame, or, with `planes` (names as for
+        render_frame_planes), (rgba, dict)."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        out = np.zeros((n, width, 4), np.uint8)
+        bufs, pl = None, None
+        if planes is not None:
+            lead = (fd.samples, n, width) if fd.samples > 1 else (n, width)
+            self._planes_struct(dict.fromkeys(planes, 0), "render_lens_frame")   # the names
+            bufs = {k: np.zeros(lead + self.PLANES[k][1], self.PLANES[k][0]) for k in planes}
+            pl = C.byref(self._planes_struct({k: b.ctypes.data for k, b in bufs.items()}, "render_lens_frame"))
+        check(self.L.mirt_render_lens_frame(self.h, C.byref(cam), C.byref(self._lens(lens)), C.byref(fd), ptr(out), pl),
+              "mirt_render_lens_frame")
+        return out if planes is None else (out, bufs)
+
+    def render_lens_frame_device(self, cam, lens, fd, d_out, d_acc=None, d_planes=None, stream=None):
+        """Enqueue a lens frame into device memory (integer device pointers);
+        d_planes maps "t" / "sphere" / "normal" to device pointers, or None."""
+        pl = C.byref(self._planes_struct(d_planes, "render_lens_frame_device")) if d_planes is not None else None
+        check(self.L.mirt_render_lens_frame_device(self.h, C.byref(cam), C.byref(self._lens(lens)), C.byref(fd),
+                                                   C.c_void_p(d_out), C.c_void_p(d_acc) if d_acc else None, pl,
+                                                   C.c_void_p(stream or 0)), "mirt_render_lens_frame_device")
+
+    def render_lens_frame_async(self, cam, lens, fd, out, planes=None):
+        """render_frame_async of a lens frame; `planes` as for
+        render_frame_planes_async, or None. Complete after wait()."""
+        arr = out.array if isinstance(out, HostBuffer) else out
+        n = check(self.L.mirt_shard_rows(C.byref(fd), None), "mirt_shard_rows")
+        if arr.nbytes < n * fd.width * 4 or not arr.flags["C_CONTIGUOUS"]:
+            raise MirtError(f"render_lens_frame_async: output holds {arr.nbytes} bytes, the shard needs "
+                            f"{n * fd.width * 4}")
+        pl = None
+        if planes is not None:
+            ptrs = {}
+            for k, buf in planes.items():
+                a = buf.array if isinstance(buf, HostBuffer) else buf
+                need = max(fd.samples, 1) * n * fd.width * (12 if k == "normal" else 4)
+                if a.nbytes < need or not a.flags["C_CONTIGUOUS"]:
+                    raise MirtError(f"render_lens_frame_async: plane {k!r} holds {a.nbytes} bytes, the frame needs "
+                                    f"{need}")
+                ptrs[k] = a.ctypes.data
+            pl = C.byref(self._planes_struct(ptrs, "render_lens_frame_async"))
+        check(self.L.mirt_render_lens_frame_async(self.h, C.byref(cam), C.byref(self._lens(lens)), C.byref(fd),
+                                                  ptr(arr), pl), "mirt_render_lens_frame_async")
 
     def share_accum(self, owner):
         """Use `owner`'s accumulation buffer (mirt_ctx_share_accum): the ctxs
@@ -1065,6 +1131,20 @@ class MultiRenderer:
         check(self.L.mirt_multi_render_frames_async(self.h, C.byref(cam), C.byref(fd), n,
                                                     abi.MULTI_FULL_GRID if full_grid else 0, cp),
               "mirt_multi_render_frames_async")
+        self.launches += 1
+
+    def render_lens_frames_async(self, cam, lens, fd, outs, nframes=None, full_grid=False):
+        """render_frames_async of lens frames (mirt_multi_render_lens_frames_async):
+        `lens` is an abi.Lens or (aperture, focus); only it travels to the ranks."""
+        n = len(outs) if outs is not None else int(nframes or 1)
+        if outs is not None:
+            arrs = [self._host(o, fd) for o in outs]
+            cp = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        else:
+            cp = None
+        check(self.L.mirt_multi_render_lens_frames_async(self.h, C.byref(cam), C.byref(Renderer._lens(lens)),
+                                                         C.byref(fd), n, abi.MULTI_FULL_GRID if full_grid else 0, cp),
+              "mirt_multi_render_lens_frames_async")
         self.launches += 1
 
     def wait(self):

@@ -626,6 +626,56 @@ int mirt_render_rays_device(mirt_ctx *ctx, const mirt_ray *d_rays, const mirt_fr
 int mirt_render_rays(mirt_ctx *ctx, const mirt_ray *rays, const mirt_frame_desc *fd, mirt_rgba8 *out,
                      const mirt_primary_planes *planes);
 
+/* Lens frames: depth of field computed in the frame's own camera pass. Each
+   pixel's thin-lens ray is made in the kernel from the pinhole's ray and the
+   pixel's RNG contract stream, so no ray buffer exists anywhere and a lens
+   frame is a frame in every respect: accumulation, shards, samples, planes, a
+   stream, every schedule, frames in flight (_async) and mirt_multi
+   (mirt_multi_render_lens_frames_async, mirt_multi.h). The lens is re-sampled
+   with fd->sample, as the accumulating loop (main.c:379-408) needs.
+   The definition (csrc/lens.h; every operation one correctly rounded binary32
+   operation, in this order), for pixel (x, y) of RNG sample s:
+     key = the frame's own key of (seed, y * width + x, s);
+     (p, d) = the pinhole's ray of that pixel and sample, with fd->jitter's
+       displacement when set (a lens frame MAY be jittered);
+     (a, b) = a point of the unit disc by rejection: try i = 0 .. 15 takes
+       a = (float)draw(key, 0x7fffff00 + 2i) / 2^31 * 2 - 1 and b likewise from
+       draw 0x7fffff00 + 2i + 1; the first try with a * a + b * b < 1 is
+       accepted, and a = b = 0 if none is. The bounce sampling's draws still
+       start at 0;
+     origin = (p + L * a) + U * b with L = cam->right * aperture and
+       U = cam->up * aperture;
+     direction = normalised ((p + d * focus) - origin), zero for a zero length.
+   Hence mirt_render_lens_frame(cam, lens, fd) is, byte for byte,
+   mirt_render_rays(mirt_lens_rays(cam, lens, fd), fd with jitter cleared), and
+   with planes element i is mirt_intersect_rays(mirt_lens_rays(...))[i].
+   aperture == 0 is the pinhole by definition: every form forwards to its plain
+   counterpart (mirt_render_frame[_planes] / _device / _async,
+   mirt_camera_rays), and the primary cache sees a plain frame. With
+   aperture > 0 and MIRT_OPT_PRIMARY_CACHE 1 a lens frame is a BYPASS (reason
+   MIRT_PCACHE_LENS) and leaves a valid cache valid.
+   Checks, errors, accumulation, mirt_ctx_share_accum chains, the folds of
+   samples > 1, empty shards and MIRT_OPT_ZERO_COPY are those of the plain call
+   of the same form; in addition MIRT_E_INVALID, before any device call, for a
+   NULL ctx, cam, lens or fd, an invalid lens (aperture not finite or < 0,
+   focus not finite or <= 0), a planes struct without a member, or planes with
+   fd->max_depth < 1. planes / d_planes may be NULL.
+   mirt_lens_rays writes the rays a lens frame traces, indexed as its colour
+   output (`samples` slabs of num_rows * width; slab j is sample + j). */
+typedef struct mirt_lens {
+    float aperture;  /* lens radius in world units; 0 = the pinhole */
+    float focus;     /* distance along the normalised pinhole ray at which the pixel is sharp */
+} mirt_lens;
+int mirt_lens_rays(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens, const mirt_frame_desc *fd,
+                   mirt_ray *out);
+int mirt_render_lens_frame(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens, const mirt_frame_desc *fd,
+                           mirt_rgba8 *out, const mirt_primary_planes *planes);
+int mirt_render_lens_frame_device(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens,
+                                  const mirt_frame_desc *fd, uint32_t *d_out, float *d_accum,
+                                  const mirt_primary_planes *d_planes, void *stream);
+int mirt_render_lens_frame_async(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens,
+                                 const mirt_frame_desc *fd, mirt_rgba8 *out, const mirt_primary_planes *planes);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
@@ -984,7 +1034,8 @@ int mirt_get_option(mirt_ctx *ctx, int option);
        (MIRT_TRAV_TILE, brute force, a tree without ordered walks,
        MIRT_OPT_FAST_SLAB / _PRUNE / _ORDERED 0, depth 0, mirt_count_frame,
        mirt_wave_stats, mirt_bounce_stats); JITTER -- fd->jitter; PLANES -- a
-       mirt_render_frame_planes* frame; RAYS -- a mirt_render_rays* frame.
+       mirt_render_frame_planes* frame; RAYS -- a mirt_render_rays* frame;
+       LENS -- a mirt_render_lens_frame* frame with aperture > 0.
      The key of every other frame, compared bitwise: what its camera rays and
        its pixel -> row map are computed from (the camera as the frame sees it:
        position, forward, and the horizontal and vertical spans; aspect, width,
@@ -1008,7 +1059,9 @@ enum { MIRT_PCACHE_BYPASS = 0, MIRT_PCACHE_FILL = 1, MIRT_PCACHE_HIT = 2 };
 enum { MIRT_PCACHE_EMPTY = 1, MIRT_PCACHE_SCENE = 2, MIRT_PCACHE_CAMERA = 3, MIRT_PCACHE_GEOMETRY = 4,
        MIRT_PCACHE_OFF = 5, /* the option is 0 (what mirt_primary_cache_stats_get then reports) */
        MIRT_PCACHE_SCHEDULE = 6, MIRT_PCACHE_JITTER = 7, MIRT_PCACHE_PLANES = 8,
-       MIRT_PCACHE_RAYS = 9 /* a ray frame (mirt_render_rays*): no camera to key by */ };
+       MIRT_PCACHE_RAYS = 9 /* a ray frame (mirt_render_rays*): no camera to key by */,
+       /* 10: a lens frame with aperture > 0 (its rays change with every sample) */
+       MIRT_PCACHE_LENS = MIRT_PCACHE_RAYS + 1 };
 typedef struct mirt_primary_cache_stats {
     uint64_t hits, fills, bypassed;   /* frames classified since the option was last set to 1 */
     uint64_t scene_id;                /* of the key; 0 when not valid */

@@ -206,6 +206,15 @@ int mirt_multi_scene_update_device(mirt_multi *m, const mirt_sphere *spheres, in
    returns. */
 int mirt_multi_render_frames_async(mirt_multi *m, const mirt_camera *cam, const mirt_frame_desc *fd, int nframes,
                                    int flags, mirt_rgba8 *const *outs);
+/* The same launch of lens frames (mirt.h mirt_lens, mirt_render_lens_frame):
+   every rank computes its rows' thin-lens rays in its own camera pass, so only
+   the 8-byte lens travels to the ranks. fd's contract, the flags, the lanes
+   and the delivery are mirt_multi_render_frames_async's; in addition
+   MIRT_E_INVALID for a NULL cam, lens or fd or an invalid lens. aperture == 0
+   is mirt_multi_render_frames_async. Frame j equals
+   mirt_render_lens_frame(cam, lens, fd with sample + j) of one context. */
+int mirt_multi_render_lens_frames_async(mirt_multi *m, const mirt_camera *cam, const mirt_lens *lens,
+                                        const mirt_frame_desc *fd, int nframes, int flags, mirt_rgba8 *const *outs);
 /* The pixel loop of main.c:356-374 (fd->accumulate 0) / main.c:379-408
    (accumulate) over all ranks: one frame into `out`. Blocking. */
 int mirt_multi_render_frame(mirt_multi *m, const mirt_camera *cam, const mirt_frame_desc *fd, mirt_rgba8 *out);
