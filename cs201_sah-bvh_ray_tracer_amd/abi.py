@@ -106,6 +106,11 @@ class Lens(C.Structure):
     _fields_ = [("aperture", C.c_float), ("focus", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """mirt_denoise_params (mirt_denoise_params_default: 3, 3, 0)"""
+    _fields_ = [("passes", C.c_int32), ("normal_sharpness", C.c_int32), ("sigma_colour", C.c_float)]
+
+
 class PrimaryCacheStats(C.Structure):
     """mirt_primary_cache_stats"""
     _fields_ = [("hits", C.c_uint64), ("fills", C.c_uint64), ("bypassed", C.c_uint64), ("scene_id", C.c_uint64),
@@ -249,6 +254,11 @@ SIGNATURES = [
     ("mirt_render_lens_frame", I, [P, P, P, P, P, P]),
     ("mirt_render_lens_frame_device", I, [P, P, P, P, P, P, P, P]),
     ("mirt_render_lens_frame_async", I, [P, P, P, P, P, P]),
+    ("mirt_denoise_params_default", None, [P]),
+    ("mirt_denoise_host", I, [I, I, P, P, I, P, P, P, P, P]),
+    ("mirt_denoise_device", I, [P, I, I, P, P, I, P, P, P, P, P, P]),
+    ("mirt_denoise", I, [P, I, I, P, P, I, P, P, P, P, P]),
+    ("mirt_render_frame_denoised", I, [P, P, P, P, P, P, P]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),
@@ -330,6 +340,7 @@ OPT_QUEUE_ORDER, OPT_DEBUG_STALL_MS = 18, 19
 OPT_CONFIRM_ONCE, OPT_DEBUG_FAIL_CONFIRM = 21, 22
 OPT_BUILD_FINISH = 23     # the device build's finish: 0 never, 1 automatic (default), 2..64 = F
 OPT_PRIMARY_CACHE = 24    # a still camera's frames start from the stored primary hits: 0 off (default), 1 on
+OPT_DENOISE_TILE = 26     # mirt_denoise*: passes of spacing 1 and 2 from an LDS tile with halo (1) or by direct loads (0)
 # mirt_primary_cache_stats: `last` (how the last frame met the cache) and `reason` (why it was no hit)
 PCACHE_BYPASS, PCACHE_FILL, PCACHE_HIT = 0, 1, 2
 PCACHE_KIND = {PCACHE_BYPASS: "bypass", PCACHE_FILL: "fill", PCACHE_HIT: "hit"}

@@ -109,6 +109,27 @@ int quality_device(ihipStream_t* stream, const mirt_node* d_nodes, int nn, int n
 // call sets it again).
 bool ctx_base_cost(const mirt_ctx* c, double* cost);
 void ctx_set_base_cost(mirt_ctx* c, double cost);
+// denoise_host.cpp: what every form of mirt_denoise checks of its arguments
+// (pointers are only compared with null).
+bool denoise_args_valid(int width, int height, const void* rgba, const void* accum, int frames, const void* sphere,
+                        const mirt_denoise_params* params, const void* out, const void* out_rgb);
+// denoise.hip: the filter's scratch, kept on the ctx (created by the first
+// call, released by mirt_destroy), and the filter of VALID arguments, all in
+// device memory, enqueued on `stream` under the name `fn` of the entry point
+// it serves. MIRT_OPT_DENOISE_TILE as stored: ctx_denoise_tile.
+struct DenoiseState;
+DenoiseState** ctx_denoise_state(mirt_ctx* c);
+void denoise_state_free(DenoiseState* st);
+int ctx_denoise_tile(const mirt_ctx* c);
+int denoise_enqueue(mirt_ctx* c, int width, int height, const uint32_t* d_rgba, const float* d_accum, int frames,
+                    const int32_t* d_sphere, const float* d_normal, const mirt_denoise_params* params,
+                    uint32_t* d_out, float* d_out_rgb, ihipStream_t* stream, const char* fn);
+// render.hip: a launch on `stream` that uses scratch the ctx keeps, outside a
+// frame. begin: the stream waits for the ctx's previous launch if that ran on
+// another stream (host_wait: the host does, whichever stream it ran on --
+// before scratch is reallocated); end: this launch is the ctx's previous one.
+int ctx_launch_begin(mirt_ctx* c, ihipStream_t* stream, bool host_wait);
+int ctx_launch_end(mirt_ctx* c, ihipStream_t* stream);
 // [p, p + bytes) is ONE page-locked host range (mirt_host_alloc /
 // mirt_host_register): copies into it are DMA, asynchronous to the host.
 bool host_page_locked(const void* p, size_t bytes);

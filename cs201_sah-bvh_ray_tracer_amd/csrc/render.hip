@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "coop.h"
+#include "denoise.h"
 #include "internal.h"
 #include "lens.h"
 #include "shard.h"
@@ -1973,6 +1974,10 @@ struct mirt_ctx {
     bool have_scene_stats = false;
     mirt_refit_stats refit_stats{};  // of the last mirt_scene_refit_device[_ptr]
     bool have_refit_stats = false;
+    mirt::DenoiseState* denoise = nullptr;  // mirt_denoise*'s scratch (denoise.hip)
+    int denoise_tile = 1;       // MIRT_OPT_DENOISE_TILE: passes of spacing 1 and 2 from an LDS tile (1) or by direct loads (0)
+    void* d_guides = nullptr;   // mirt_render_frame_denoised: the frame's sphere and normal planes
+    size_t guides_cap = 0;
 };
 
 namespace {
@@ -2735,9 +2740,10 @@ void mirt_destroy(mirt_ctx* c)
     if (c->slab_guard) (void)hipEventSynchronize(c->slab_free);   // another stream's read of the slab
     accum_release(c->acc);
     mirt::build_state_free(c->build);
+    mirt::denoise_state_free(c->denoise);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
-                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d})
+                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d, c->d_guides})
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3039,6 +3045,21 @@ int enqueue_frame_device(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_d
 int ctx_device(const mirt_ctx* c) { return c->device; }
 int ctx_build_finish(const mirt_ctx* c) { return c->build_finish; }
 BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
+DenoiseState** ctx_denoise_state(mirt_ctx* c) { return &c->denoise; }
+int ctx_denoise_tile(const mirt_ctx* c) { return c->denoise_tile; }
+int ctx_launch_begin(mirt_ctx* c, hipStream_t s, bool host_wait)
+{
+    if (c->launched && host_wait) HIP_TRY(hipEventSynchronize(c->done));
+    if (c->launched && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->done, 0));
+    return MIRT_OK;
+}
+int ctx_launch_end(mirt_ctx* c, hipStream_t s)
+{
+    HIP_TRY(hipEventRecord(c->done, s));
+    c->last_stream = s;
+    c->launched = true;
+    return MIRT_OK;
+}
 int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
 {
     Scene* sn = new (std::nothrow) Scene();
@@ -3444,6 +3465,63 @@ int mirt_lens_rays(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, c
     }
     if (bytes) HIP_TRY(hipMemcpyAsync(out, c->d_res, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+// ---- a frame and its filtered display (csrc/denoise.h)
+
+int mirt_render_frame_denoised(mirt_ctx* c, const mirt_camera* cam, const mirt_lens* lens, const mirt_frame_desc* fd,
+                               const mirt_denoise_params* params, mirt_rgba8* out, mirt_rgba8* raw)
+{
+    const char* fn = "mirt_render_frame_denoised";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!cam || !frame_desc_valid(fd) || (lens && !lens_valid(lens)) || !denoise_params_valid(params) || !out ||
+        fd->num_shards != 1 || fd->max_depth < 1) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    if (accum_chain(c)) {
+        set_error("%s: the context shares its accumulation buffer (mirt_ctx_share_accum)", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
+    // the planes of the frame's `samples` slabs, spheres then normals, then
+    // the filtered display; the filter is guided by the last slab's planes,
+    // those of the frame its source shows
+    const size_t n = (size_t)fd->width * fd->height, slabs = fd->samples > 1 ? fd->samples : 1;
+    // (the blocking call leaves nothing in flight that uses the buffer: it may grow at once)
+    if (int rc = ensure(&c->d_guides, &c->guides_cap, 16 * n * slabs + 4 * n)) return rc;
+    int32_t* const d_sphere = (int32_t*)c->d_guides;
+    float* const d_normal = (float*)(d_sphere + n * slabs);
+    uint32_t* const d_filtered = (uint32_t*)(d_normal + 3 * n * slabs);
+    const size_t row = (size_t)fd->width * 4;   // copies out as enqueue_host_frame's: rows x width
+    const LensConst lc = lens ? lens_const(cam, lens) : LensConst{};
+    if (lens && lens->aperture != 0.0f) c->lens = &lc;   // aperture 0 is the pinhole: the plain frame
+    c->planes = Planes{nullptr, d_sphere, d_normal};
+    c->lone_frame = true;
+    uint32_t* disp = nullptr;
+    int rc = enqueue_frame(c, cam, fd, nullptr, &disp, fn);
+    c->lone_frame = false;
+    c->planes = Planes{};
+    c->lens = nullptr;
+    if (rc) return rc;
+    // the source: the accumulation buffer as the frame's last fold left it
+    // (the ctx's own: its frames store into it on this stream), with that
+    // frame's divisor, or the last slab's display
+    const int frames = fd->accumulate ? fd->frames + (int)slabs - 1 : 1;
+    rc = denoise_enqueue(c, fd->width, fd->height, fd->accumulate ? nullptr : disp,
+                         fd->accumulate ? c->acc->d_acc : nullptr, frames, d_sphere + n * (slabs - 1),
+                         d_normal + 3 * n * (slabs - 1), params, d_filtered, nullptr, c->stream, fn);
+    if (rc) return rc;
+    // both copies behind the filter (it leaves the display slab alone): a copy
+    // into pageable memory holds the host, and the filter's launches with it
+    if (raw) HIP_TRY(hipMemcpy2DAsync(raw, row, disp, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, row, d_filtered, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
 }
 
@@ -4134,6 +4212,10 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         if (value != 1 && value != 2 && value != 4 && value != 8) break;
         c->block_waves = value;
         return MIRT_OK;
+    case MIRT_OPT_DENOISE_TILE:
+        if (value != 0 && value != 1) break;
+        c->denoise_tile = value;
+        return MIRT_OK;
     case MIRT_OPT_PRIMARY_CACHE:
         if (value != 0 && value != 1) break;
         if (value == 0 && c->pc.d) {
@@ -4174,6 +4256,7 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_DEBUG_FAIL_CONFIRM) return c->debug_fail_confirm;
     if (option == MIRT_OPT_BUILD_FINISH) return c->build_finish;
     if (option == MIRT_OPT_PRIMARY_CACHE) return c->pc.on;
+    if (option == MIRT_OPT_DENOISE_TILE) return c->denoise_tile;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
     set_error("mirt_get_option: bad option %d", option);
     return MIRT_E_INVALID;

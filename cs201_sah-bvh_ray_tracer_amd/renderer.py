@@ -714,6 +714,73 @@ class Renderer:
         check(self.L.mirt_render_lens_frame_async(self.h, C.byref(cam), C.byref(self._lens(lens)), C.byref(fd),
                                                   ptr(arr), pl), "mirt_render_lens_frame_async")
 
+    # ---- denoising (an edge-avoiding a-trous filter guided by the primary-hit planes)
+    @staticmethod
+    def _denoise_params(params):
+        """abi.DenoiseParams from one, from (passes, normal_sharpness, sigma_colour), or the defaults for None."""
+        if isinstance(params, abi.DenoiseParams):
+            return params
+        p = abi.DenoiseParams()
+        load().mirt_denoise_params_default(C.byref(p))
+        if params is not None:
+            p.passes, p.normal_sharpness, p.sigma_colour = params
+        return p
+
+    def denoise(self, sphere, normal=None, rgba=None, accum=None, frames=1, params=None, out=None, rgb=False,
+                stream=None):
+        """The filter of mirt.h's mirt_denoise_params on an image given as
+        numpy arrays (mirt_denoise: blocking) or as torch tensors on the ctx's
+        device (mirt_denoise_device: enqueued on `stream`, an integer
+        hipStream_t, 0 / None = the default stream, not waited for). sphere:
+        (H, W) int32; normal: (H, W, 3) float32 or None; the colours either
+        rgba (H, W, 4) uint8 or accum (H, W, 3) float32 with its divisor
+        `frames`. Returns the (H, W, 4) uint8 display, or with rgb=True
+        (display, (H, W, 3) float32). `out` (device form): the uint8 tensor the
+        display goes to, which may be `rgba` itself."""
+        p = self._denoise_params(params)
+        src = rgba if rgba is not None else accum
+        if src is None or (rgba is not None and accum is not None):
+            raise MirtError("denoise: give exactly one of rgba and accum")
+        h, w = sphere.shape
+        if not isinstance(sphere, np.ndarray):   # device tensors
+            import torch
+            for t, dtype in ((sphere, torch.int32), (normal, torch.float32), (rgba, torch.uint8),
+                             (accum, torch.float32), (out, torch.uint8)):
+                if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dtype):
+                    raise MirtError("denoise: tensors must be contiguous, on the device, int32 / float32 / uint8")
+            if out is None:
+                out = torch.empty((h, w, 4), dtype=torch.uint8, device=sphere.device)
+            out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=sphere.device) if rgb else None
+            dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            check(self.L.mirt_denoise_device(self.h, w, h, dp(rgba), dp(accum), frames, dp(sphere), dp(normal),
+                                             C.byref(p), dp(out), dp(out_rgb), C.c_void_p(stream or 0)),
+                  "mirt_denoise_device")
+            return (out, out_rgb) if rgb else out
+        sphere = np.ascontiguousarray(sphere, np.int32)
+        normal = None if normal is None else np.ascontiguousarray(normal, np.float32)
+        rgba = None if rgba is None else np.ascontiguousarray(rgba, np.uint8)
+        accum = None if accum is None else np.ascontiguousarray(accum, np.float32)
+        res = np.zeros((h, w, 4), np.uint8)
+        out_rgb = np.zeros((h, w, 3), np.float32) if rgb else None
+        check(self.L.mirt_denoise(self.h, w, h, ptr(rgba), ptr(accum), frames, ptr(sphere), ptr(normal), C.byref(p),
+                                  ptr(res), ptr(out_rgb)), "mirt_denoise")
+        return (res, out_rgb) if rgb else res
+
+    def render_frame_denoised(self, cam, width, height, lens=None, params=None, raw=False, **frame_desc_args):
+        """render_frame (frame_desc's keyword arguments; one shard), through
+        `lens` if given, and its filtered display (mirt_render_frame_denoised):
+        the filter's source is the accumulation buffer with accumulate=True,
+        else the frame's display; the accumulation buffer is left as the plain
+        call leaves it. Returns the filtered (height, width, 4) uint8 display,
+        or with raw=True (filtered, the display render_frame returns)."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        out = np.zeros((height, width, 4), np.uint8)
+        plain = np.zeros((height, width, 4), np.uint8) if raw else None
+        check(self.L.mirt_render_frame_denoised(self.h, C.byref(cam), C.byref(self._lens(lens)) if lens is not None
+                                                else None, C.byref(fd), C.byref(self._denoise_params(params)),
+                                                ptr(out), ptr(plain)), "mirt_render_frame_denoised")
+        return (out, plain) if raw else out
+
     def share_accum(self, owner):
         """Use `owner`'s accumulation buffer (mirt_ctx_share_accum): the ctxs
         of one accumulating display loop with frames in flight; None: a

@@ -676,6 +676,92 @@ int mirt_render_lens_frame_device(mirt_ctx *ctx, const mirt_camera *cam, const m
 int mirt_render_lens_frame_async(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens,
                                  const mirt_frame_desc *fd, mirt_rgba8 *out, const mirt_primary_planes *planes);
 
+/* Denoising a frame where it lies: an edge-avoiding a-trous filter guided by
+   the frame's primary-hit planes (mirt_primary_planes' sphere and normal). A
+   one-sample frame is noisy -- each hit adds half of one random bounce chain
+   (renderer.c:51-58) -- and the accumulating loop (main.c:379-408) needs many
+   frames of a still camera; the filter averages a pixel with its neighbours on
+   the same sphere and of like normal, in device memory, on the frame's stream.
+   The definition (csrc/denoise.h; every operation one correctly rounded
+   binary32 operation, in this order), for an image of width x height pixels,
+   row-major, pixel i = y * width + x:
+     colour source, exactly one of: rgba, packed RGBA8 as a frame's display,
+       c[ch] = (float)u8 / 255.0f (main.c:368-370); or accum, float3 sums as
+       the accumulation buffer holds them, with a divisor frames >= 1,
+       c[ch] = a[ch] / (float)frames;
+     guides: sphere (int32 per pixel, < 0 on a miss; required) and normal
+       (three floats per pixel; may be NULL);
+     pass i = 0 .. passes - 1 has tap spacing s = 2^i, reads the colours of the
+       pass before it (pass 0: the source) and writes a new image. For pixel
+       p = (x, y) the taps q = (x + dx s, y + dy s) are visited dy = -2 .. 2
+       outermost, dx = -2 .. 2 innermost. A tap outside the image, or with
+       sphere[q] != sphere[p], contributes nothing (two misses are equal).
+       Else w = B[dy + 2] * B[dx + 2], B = {1/16, 1/4, 3/8, 1/4, 1/16}; the
+       centre tap keeps exactly that (9/64: the weight sum is never zero);
+       every other tap, with a normal plane and sphere[p] >= 0:
+         d = nx_p nx_q; d = d + ny_p ny_q; d = d + nz_p nz_q; m = fmaxf(d, 0);
+         m = m * m, normal_sharpness times; w = w * m
+       and with sigma_colour > 0:
+         e = c_p - c_q per channel, of this pass's input;
+         g = er er; g = g + eg eg; g = g + eb eb;
+         w = w * (1.0f / (1.0f + g * inv_i)),
+         inv_0 = 1.0f / (sigma_colour * sigma_colour), inv_{i+1} = inv_i * 4.0f.
+       sw = sw + w and sc[ch] = sc[ch] + c_q[ch] * w in visiting order from
+       +0.0f; the pass's colour is sc[ch] / sw;
+     after the last pass out_rgb (may be NULL) receives the three floats per
+       pixel and out (may be NULL; not both) the RGBA8
+       (uint8_t)(int)fminf(c * 255.0f, 255.0f) per channel (main.c:398-400's
+       cast), alpha 255.
+   Non-finite colours or normals give unspecified values, never an access
+   outside the image or the scratch.
+   MIRT_E_INVALID, before any device call: NULL ctx (not mirt_denoise_host),
+   params or sphere plane; both or neither colour source; frames < 1 with
+   accum; no output; width or height < 1, or width * height beyond 2^31 (the
+   frame descriptor's limit); passes outside 1..5; normal_sharpness outside
+   0..7; sigma_colour negative or not finite.
+   mirt_denoise_host: the filter on the host (no device call, no ctx).
+   mirt_denoise_device: everything in device memory; enqueued on `stream`
+   (NULL: the default stream), returns without waiting; byte for byte the host
+   form's result. The ping-pong images are scratch the ctx keeps (grown like
+   its other buffers, released by mirt_destroy); a launch on another stream
+   than the ctx's previous launch first waits for that one (an event), as
+   frames do. d_out may alias d_rgba.
+   mirt_denoise: blocking, host pointers: copies in, filters on the ctx's
+   stream, copies out.
+   mirt_render_frame_denoised: blocking; renders exactly what
+   mirt_render_frame_planes (lens NULL or aperture 0) or mirt_render_lens_frame
+   renders -- colours and accumulation buffer byte for byte the plain call's,
+   the sphere and normal planes into buffers the ctx keeps -- then filters
+   fd->accumulate ? the accumulation buffer after the last fold, with that
+   frame's divisor : the last slab's display. `out` receives the filtered
+   display, `raw` (may be NULL) the display mirt_render_frame would return.
+   The accumulation buffer is not touched, so the loop of main.c:379-408
+   continues unbiased. In addition MIRT_E_INVALID, before any device call, for
+   a NULL cam, fd or out, an invalid fd or lens, fd->num_shards != 1,
+   fd->max_depth < 1, or a ctx in a mirt_ctx_share_accum chain. Under
+   MIRT_OPT_PRIMARY_CACHE the frame is a BYPASS (PLANES; LENS through a lens),
+   as any planes frame is: a still camera keeps the first frame's planes and
+   calls mirt_denoise_device behind plain cached frames.
+   mirt_multi and sharded images are out of scope. */
+typedef struct mirt_denoise_params {
+    int32_t passes;            /* 1..5; pass i has tap spacing 2^i */
+    int32_t normal_sharpness;  /* 0..7: the normals' cosine is squared this many times */
+    float sigma_colour;        /* >= 0; 0 = no colour weight */
+} mirt_denoise_params;
+void mirt_denoise_params_default(mirt_denoise_params *out);   /* 3, 3, 0 */
+int mirt_denoise_host(int width, int height, const mirt_rgba8 *rgba, const float *accum, int frames,
+                      const int32_t *sphere, const float *normal, const mirt_denoise_params *params,
+                      mirt_rgba8 *out, float *out_rgb);
+int mirt_denoise_device(mirt_ctx *ctx, int width, int height, const uint32_t *d_rgba, const float *d_accum,
+                        int frames, const int32_t *d_sphere, const float *d_normal,
+                        const mirt_denoise_params *params, uint32_t *d_out, float *d_out_rgb, void *stream);
+int mirt_denoise(mirt_ctx *ctx, int width, int height, const mirt_rgba8 *rgba, const float *accum, int frames,
+                 const int32_t *sphere, const float *normal, const mirt_denoise_params *params, mirt_rgba8 *out,
+                 float *out_rgb);
+int mirt_render_frame_denoised(mirt_ctx *ctx, const mirt_camera *cam, const mirt_lens *lens,
+                               const mirt_frame_desc *fd, const mirt_denoise_params *params, mirt_rgba8 *out,
+                               mirt_rgba8 *raw);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
@@ -1005,7 +1091,7 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        100k), else 0 (behind at 1M). Every other value is
                                        MIRT_E_INVALID; mirt_get_option reads back the stored
                                        value. Speed only: the same bytes under every setting. */
-       MIRT_OPT_PRIMARY_CACHE = 24  /* a still camera (main.c:379-408's accumulating loop): 1 = the
+       MIRT_OPT_PRIMARY_CACHE = 24, /* a still camera (main.c:379-408's accumulating loop): 1 = the
                                        ctx keeps the camera rays' closest hits (t, sphere) of one
                                        slab, 8 bytes per shard pixel, and a frame whose camera
                                        rays are those of the frame that stored them starts from
@@ -1013,7 +1099,12 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        mirt_primary_cache_stats); 0 (default) = off: waits for the
                                        ctx's frames and releases the memory. Every other value is
                                        MIRT_E_INVALID; mirt_get_option reads back the stored
-                                       value. Speed only: the same bytes under either setting. */ };
+                                       value. Speed only: the same bytes under either setting. */
+       MIRT_OPT_DENOISE_TILE = 26   /* mirt_denoise*: the passes of spacing 1 and 2 take their taps
+                                       from an LDS tile with halo (1, default:
+                                       MEASUREMENTS.md E) or by direct loads (0). Every other value is
+                                       MIRT_E_INVALID. Speed only: the same bytes under either
+                                       setting. (25 is not assigned.) */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back
