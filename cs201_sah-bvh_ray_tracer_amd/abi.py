@@ -111,6 +111,22 @@ class DenoiseParams(C.Structure):
     _fields_ = [("passes", C.c_int32), ("normal_sharpness", C.c_int32), ("sigma_colour", C.c_float)]
 
 
+class ReprojectParams(C.Structure):
+    """mirt_reproject_params (mirt_reproject_params_default: 64, 4, 1/64)"""
+    _fields_ = [("max_history", C.c_int32), ("taps", C.c_int32), ("t_tolerance", C.c_float)]
+
+
+class HistoryStats(C.Structure):
+    """mirt_history_stats"""
+    _fields_ = [("frames", C.c_uint64), ("scene_id", C.c_uint64), ("bytes", C.c_uint64), ("reused", C.c_uint64),
+                ("fresh", C.c_uint64), ("sky", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+# mirt_history_px: the mean of n samples (n == 0: no history)
+HISTORY = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("n", np.int32)])
+assert HISTORY.itemsize == 16
+
+
 class PrimaryCacheStats(C.Structure):
     """mirt_primary_cache_stats"""
     _fields_ = [("hits", C.c_uint64), ("fills", C.c_uint64), ("bypassed", C.c_uint64), ("scene_id", C.c_uint64),
@@ -259,6 +275,14 @@ SIGNATURES = [
     ("mirt_denoise_device", I, [P, I, I, P, P, I, P, P, P, P, P, P]),
     ("mirt_denoise", I, [P, I, I, P, P, I, P, P, P, P, P]),
     ("mirt_render_frame_denoised", I, [P, P, P, P, P, P, P]),
+    ("mirt_reproject_params_default", None, [P]),
+    ("mirt_reproject_host", I, [I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject_device", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_render_frame_reprojected", I, [P, P, P, P, P, P]),
+    ("mirt_history_reset", I, [P]),
+    ("mirt_history_stats_get", I, [P, P]),
+    ("mirt_history_read", I, [P, P, C.c_size_t]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),

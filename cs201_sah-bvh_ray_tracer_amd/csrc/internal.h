@@ -124,6 +124,25 @@ int ctx_denoise_tile(const mirt_ctx* c);
 int denoise_enqueue(mirt_ctx* c, int width, int height, const uint32_t* d_rgba, const float* d_accum, int frames,
                     const int32_t* d_sphere, const float* d_normal, const mirt_denoise_params* params,
                     uint32_t* d_out, float* d_out_rgb, ihipStream_t* stream, const char* fn);
+// reproject_host.cpp: what every form of mirt_reproject checks of its
+// arguments (pointers are only compared with null and with each other).
+bool reproject_args_valid(int width, int height, const void* cam, const void* cam_prev, const void* rgba, const void* t,
+                          const void* sphere, const void* hist, const void* t_prev, const void* sphere_prev,
+                          const mirt_reproject_params* params, const void* hist_out);
+// reproject.hip: the history of mirt_render_frame_reprojected, kept on the ctx
+// (created by the first call, released by mirt_destroy). begin: the history is
+// emptied if the image or the scene is not the one it was made of, and
+// *d_t / *d_sphere are where the frame about to be enqueued stores its planes;
+// end: the frame's display d_rgba is reprojected from the history on `stream`
+// into the pair's other half, which becomes the history; *d_shown = the
+// display of the new records.
+struct ReprojectState;
+ReprojectState** ctx_reproject_state(mirt_ctx* c);
+void reproject_state_free(ReprojectState* st);
+int reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, float** d_t, int32_t** d_sphere,
+                          const char* fn);
+int reproject_frame_end(mirt_ctx* c, const mirt_camera* cam, const uint32_t* d_rgba,
+                        const mirt_reproject_params* params, const uint32_t** d_shown, ihipStream_t* stream);
 // render.hip: a launch on `stream` that uses scratch the ctx keeps, outside a
 // frame. begin: the stream waits for the ctx's previous launch if that ran on
 // another stream (host_wait: the host does, whichever stream it ran on --

@@ -21,6 +21,7 @@
 #include "denoise.h"
 #include "internal.h"
 #include "lens.h"
+#include "reproject.h"
 #include "shard.h"
 #include "trace.h"
 
@@ -1978,6 +1979,7 @@ struct mirt_ctx {
     int denoise_tile = 1;       // MIRT_OPT_DENOISE_TILE: passes of spacing 1 and 2 from an LDS tile (1) or by direct loads (0)
     void* d_guides = nullptr;   // mirt_render_frame_denoised: the frame's sphere and normal planes
     size_t guides_cap = 0;
+    mirt::ReprojectState* reproject = nullptr;  // mirt_render_frame_reprojected's history (reproject.hip)
 };
 
 namespace {
@@ -2741,6 +2743,7 @@ void mirt_destroy(mirt_ctx* c)
     accum_release(c->acc);
     mirt::build_state_free(c->build);
     mirt::denoise_state_free(c->denoise);
+    mirt::reproject_state_free(c->reproject);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
                     (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d, c->d_guides})
@@ -3047,6 +3050,7 @@ int ctx_build_finish(const mirt_ctx* c) { return c->build_finish; }
 BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 DenoiseState** ctx_denoise_state(mirt_ctx* c) { return &c->denoise; }
 int ctx_denoise_tile(const mirt_ctx* c) { return c->denoise_tile; }
+ReprojectState** ctx_reproject_state(mirt_ctx* c) { return &c->reproject; }
 int ctx_launch_begin(mirt_ctx* c, hipStream_t s, bool host_wait)
 {
     if (c->launched && host_wait) HIP_TRY(hipEventSynchronize(c->done));
@@ -3520,6 +3524,47 @@ int mirt_render_frame_denoised(mirt_ctx* c, const mirt_camera* cam, const mirt_l
     // into pageable memory holds the host, and the filter's launches with it
     if (raw) HIP_TRY(hipMemcpy2DAsync(raw, row, disp, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpy2DAsync(out, row, d_filtered, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    return MIRT_OK;
+}
+
+// ---- a frame and the display of its reprojected history (csrc/reproject.h)
+
+int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd,
+                                  const mirt_reproject_params* params, mirt_rgba8* out, mirt_rgba8* raw)
+{
+    const char* fn = "mirt_render_frame_reprojected";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!cam || !frame_desc_valid(fd) || !reproject_params_valid(params) || !out || fd->accumulate != 0 ||
+        fd->samples > 1 || fd->num_shards != 1 || fd->jitter != 0 || fd->max_depth < 1) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    if (accum_chain(c)) {
+        set_error("%s: the context shares its accumulation buffer (mirt_ctx_share_accum)", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
+    float* d_t = nullptr;
+    int32_t* d_sphere = nullptr;
+    if (int rc = reproject_frame_begin(c, fd->width, fd->height, scene_of(c)->id, &d_t, &d_sphere, fn)) return rc;
+    c->planes = Planes{d_t, d_sphere, nullptr};
+    c->lone_frame = true;
+    uint32_t* disp = nullptr;
+    int rc = enqueue_frame(c, cam, fd, nullptr, &disp, fn);
+    c->lone_frame = false;
+    c->planes = Planes{};
+    if (rc) return rc;
+    const uint32_t* shown = nullptr;
+    rc = reproject_frame_end(c, cam, disp, params, &shown, c->stream);
+    if (rc) return rc;
+    const size_t row = (size_t)fd->width * 4;   // copies out as enqueue_host_frame's: rows x width
+    if (raw) HIP_TRY(hipMemcpy2DAsync(raw, row, disp, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, row, shown, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;

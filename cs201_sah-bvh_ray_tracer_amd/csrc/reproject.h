@@ -1,0 +1,224 @@
+// The reprojection of a frame's history of mirt_reproject* (include/mirt.h
+// mirt_reproject_params), stated once for the host form (reproject_host.cpp)
+// and the kernels (reproject.hip). Under -ffp-contract=off every operation
+// below is one correctly rounded binary32 operation, in the order written
+// (tests/reproject_cases.py restates it in numpy, bit for bit); sqrtf is the
+// correctly rounded root (trace.h sqrt_rn32 has why that spelling serves).
+//
+// An image of width x height pixels, row-major, pixel i = y * width + x,
+// unsharded. Two cameras, the current one and the previous one, each as the
+// constants make_frame_const computes (render.hip; ReprojectCam below): position
+// p, forward, right, up, sw = 2 half_w, sh = 2 half_h, hor = right * sw,
+// ver = up * sh, aspect, wf, hf. Per pixel of the current frame: rgba (the
+// display of a one-sample frame), t and sphere (mirt_primary_planes). Per
+// pixel of the previous frame: hist = {r, g, b, n}, the mean of n samples
+// (n == 0: no history), t_prev and sphere_prev. Without a previous frame every
+// pixel takes "no history". For pixel (x, y):
+//
+//  1 c[ch] = (float)u8 / 255.0f (main.c:368-370); s = sphere[i]. s < 0: no
+//    history (the sky carries no noise).
+//  2 d = the unjittered pinhole direction of (x, y) under the current camera
+//    (render.hip camera_ray's arithmetic, normalize3 included: zero for a zero
+//    length); X[k] = p[k] + d[k] * t[i].
+//  3 e[k] = X[k] - p_prev[k]; zf = dot3(e, forward_prev), left to right.
+//    !(zf > 0.0f): no history.
+//  4 a = dot3(e, right_prev) / zf; b = dot3(e, up_prev) / zf; u = a / sw_prev;
+//    v = b / sh_prev; xf = (u / aspect + 0.5f) * wf; yf = (0.5f - v) * hf
+//    (the inverse of main.c:362-365).
+//  5 l = sqrtf(dot3(e, e)).
+//  6 taps == 1: gx = floorf(xf + 0.5f), gy likewise; one tap (gx, gy), w = 1.0f.
+//    taps == 4: gx = floorf(xf), gy = floorf(yf), ax = xf - gx, ay = yf - gy;
+//    the taps in this order: (gx, gy) with (1 - ax) * (1 - ay), (gx + 1, gy)
+//    with ax * (1 - ay), (gx, gy + 1) with (1 - ax) * ay, (gx + 1, gy + 1)
+//    with ax * ay.
+//  7 A tap (tx, ty) is kept as floats and is inside iff tx >= 0.0f && tx < wf
+//    && ty >= 0.0f && ty < hf; only then is it cast to int. NaN or infinite
+//    coordinates fail every comparison: no position computed from the data
+//    ever indexes outside the image.
+//  8 An inside tap q is valid iff w > 0.0f, sphere_prev[q] == s,
+//    hist[q].n >= 1 and fabsf(l - t_prev[q]) <= t_tolerance * l (which rejects
+//    the far side, or another part, of the same sphere).
+//  9 Over the valid taps, in visiting order, from +0.0f: sw_ = sw_ + w,
+//    sc[ch] = sc[ch] + hist[q].c[ch] * w, nmin = min n. No valid tap: no
+//    history. Else m[ch] = sc[ch] / sw_.
+// 10 n_new = min(nmin + 1, max_history); mean[ch] = m[ch] + (c[ch] - m[ch]) /
+//    (float)n_new. No history: n_new = 1, mean = c.
+// 11 hist_out[i] = {mean, n_new}; out: RGBA8 by denoise_display's cast of
+//    mean; out_rgb: the three floats of mean.
+//
+// Unlike the denoiser's, the tap positions depend on the data; step 7 is what
+// keeps every access inside the image whatever t holds.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/mirt.h"
+#include "denoise.h"   // denoise_size_valid, denoise_display
+#include "rng.h"       // MIRT_HD
+
+namespace mirt {
+
+constexpr int kReprojectMaxHistory = 65536;
+
+// A camera as the frames see it (make_frame_const's expressions, computed on
+// the host: libm tan stays there).
+struct ReprojectCam {
+    float p[3], fwd[3], right[3], up[3];
+    float hor[3], ver[3];   // right * sw, up * sh
+    float sw, sh;
+    float aspect, wf, hf;
+};
+
+inline ReprojectCam reproject_cam(const mirt_camera* cam, int width, int height)
+{
+    ReprojectCam r{};
+    const float aspect = (float)width / (float)height;
+    const float fov_rad = (float)((double)cam->fov * (M_PI / 180.0));
+    const float half_h = (float)std::tan((double)(fov_rad / 2.0f));
+    const float half_w = aspect * half_h;
+    r.sw = 2.0f * half_w;
+    r.sh = 2.0f * half_h;
+    r.p[0] = cam->position.x; r.p[1] = cam->position.y; r.p[2] = cam->position.z;
+    r.fwd[0] = cam->forward.x; r.fwd[1] = cam->forward.y; r.fwd[2] = cam->forward.z;
+    r.right[0] = cam->right.x; r.right[1] = cam->right.y; r.right[2] = cam->right.z;
+    r.up[0] = cam->up.x; r.up[1] = cam->up.y; r.up[2] = cam->up.z;
+    for (int k = 0; k < 3; k++) {
+        r.hor[k] = r.right[k] * r.sw;
+        r.ver[k] = r.up[k] * r.sh;
+    }
+    r.aspect = aspect;
+    r.wf = (float)width;
+    r.hf = (float)height;
+    return r;
+}
+
+inline bool reproject_params_valid(const mirt_reproject_params* p)
+{
+    return p && p->max_history >= 1 && p->max_history <= kReprojectMaxHistory && (p->taps == 1 || p->taps == 4) &&
+           std::isfinite(p->t_tolerance) && p->t_tolerance >= 0.0f;
+}
+
+MIRT_HD float reproject_dot3(const float a[3], const float b[3])   // trace.h dot3: left to right
+{
+    float s = a[0] * b[0];
+    s = s + a[1] * b[1];
+    return s + a[2] * b[2];
+}
+
+// What became of a pixel (mirt_history_stats counts them).
+enum { kReprojectSky = 0, kReprojectFresh = 1, kReprojectReused = 2 };
+
+// Pixel (x, y)'s new record, from its own rgba, t and s = sphere. has_prev
+// false: no previous frame (prev is not looked at). `at` gives the previous frame at an index INSIDE the
+// image: at.hist(q), at.t(q), at.sphere(q). TAPS: 1 or 4. *kind: one of the
+// three above.
+template <int TAPS, class At>
+MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const ReprojectCam& prev, bool has_prev, const At& at,
+                                        int width, int x, int y, uint32_t rgba, float t, int32_t s, int max_history,
+                                        float t_tolerance, int* kind)
+{
+    const float c[3] = {(float)(rgba & 0xffu) / 255.0f, (float)((rgba >> 8) & 0xffu) / 255.0f,
+                        (float)((rgba >> 16) & 0xffu) / 255.0f};
+    mirt_history_px fresh{c[0], c[1], c[2], 1};
+    *kind = s < 0 ? kReprojectSky : kReprojectFresh;
+    if (s < 0 || !has_prev) return fresh;
+    // 2: the hit point
+    const float u0 = ((float)x / cur.wf - 0.5f) * cur.aspect;
+    const float v0 = -((float)y / cur.hf - 0.5f);
+    float d[3];
+    for (int k = 0; k < 3; k++) {
+        d[k] = cur.fwd[k] + cur.hor[k] * u0;
+        d[k] = d[k] + cur.ver[k] * v0;
+    }
+    float sq = d[0] * d[0];
+    sq = sq + d[1] * d[1];
+    sq = sq + d[2] * d[2];
+    const float len = __builtin_sqrtf(sq);
+    for (int k = 0; k < 3; k++) d[k] = len != 0.0f ? d[k] / len : 0.0f;
+    // 3 .. 5: where the previous camera saw it, and how far away
+    float e[3];
+    for (int k = 0; k < 3; k++) {
+        const float X = cur.p[k] + d[k] * t;
+        e[k] = X - prev.p[k];
+    }
+    const float zf = reproject_dot3(e, prev.fwd);
+    if (!(zf > 0.0f)) return fresh;
+    const float a = reproject_dot3(e, prev.right) / zf;
+    const float b = reproject_dot3(e, prev.up) / zf;
+    const float u = a / prev.sw;
+    const float v = b / prev.sh;
+    const float xf = (u / prev.aspect + 0.5f) * prev.wf;
+    const float yf = (0.5f - v) * prev.hf;
+    const float l = __builtin_sqrtf(reproject_dot3(e, e));
+    // 6: the taps
+    float tx[TAPS], ty[TAPS], w[TAPS];
+    if (TAPS == 1) {
+        tx[0] = floorf(xf + 0.5f);
+        ty[0] = floorf(yf + 0.5f);
+        w[0] = 1.0f;
+    } else {
+        const float gx = floorf(xf), gy = floorf(yf);
+        const float ax = xf - gx, ay = yf - gy;
+        const float bx = 1.0f - ax, by = 1.0f - ay;
+        tx[0] = gx;             ty[0] = gy;             w[0] = bx * by;
+        tx[1 % TAPS] = gx + 1.0f; ty[1 % TAPS] = gy;        w[1 % TAPS] = ax * by;
+        tx[2 % TAPS] = gx;        ty[2 % TAPS] = gy + 1.0f; w[2 % TAPS] = bx * ay;
+        tx[3 % TAPS] = gx + 1.0f; ty[3 % TAPS] = gy + 1.0f; w[3 % TAPS] = ax * ay;
+    }
+    // 7: every tap's loads before any is used, unconditionally (a tap that is
+    // not inside reads the pixel's own index and is dropped), so that the
+    // kernels issue them together
+    const size_t self = (size_t)y * width + x;
+    bool inside[TAPS];
+    mirt_history_px hq[TAPS];
+    float tq[TAPS];
+    int32_t sq_[TAPS];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int j = 0; j < TAPS; j++) {
+        inside[j] = tx[j] >= 0.0f && tx[j] < prev.wf && ty[j] >= 0.0f && ty[j] < prev.hf;
+        const size_t q = inside[j] ? (size_t)(int)ty[j] * width + (int)tx[j] : self;
+        hq[j] = at.hist(q);
+        tq[j] = at.t(q);
+        sq_[j] = at.sphere(q);
+    }
+    // 8, 9
+    float sw_ = 0.0f, sc[3] = {0.0f, 0.0f, 0.0f};
+    int32_t nmin = 0;
+    bool any = false;
+    const float bound = t_tolerance * l;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int j = 0; j < TAPS; j++) {
+        if (!inside[j] || !(w[j] > 0.0f) || sq_[j] != s || hq[j].n < 1 || !(fabsf(l - tq[j]) <= bound)) continue;
+        sw_ = sw_ + w[j];
+        sc[0] = sc[0] + hq[j].r * w[j];
+        sc[1] = sc[1] + hq[j].g * w[j];
+        sc[2] = sc[2] + hq[j].b * w[j];
+        nmin = any && nmin < hq[j].n ? nmin : hq[j].n;
+        any = true;
+    }
+    if (!any) return fresh;
+    // 10 (nmin + 1 without the overflow an unchecked record could provoke)
+    const int32_t n_new = nmin >= max_history ? max_history : nmin + 1;
+    const float nf = (float)n_new;
+    mirt_history_px out;
+    const float m0 = sc[0] / sw_, m1 = sc[1] / sw_, m2 = sc[2] / sw_;
+    out.r = m0 + (c[0] - m0) / nf;
+    out.g = m1 + (c[1] - m1) / nf;
+    out.b = m2 + (c[2] - m2) / nf;
+    out.n = n_new;
+    if (n_new > 1) *kind = kReprojectReused;
+    return out;
+}
+
+// 11: the display of a record
+MIRT_HD uint32_t reproject_display(const mirt_history_px& h)
+{
+    return denoise_display(DenoiseColour{h.r, h.g, h.b, 0});
+}
+
+}  // namespace mirt

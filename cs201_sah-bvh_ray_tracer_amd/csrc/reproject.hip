@@ -1,0 +1,382 @@
+// mirt_reproject_device / mirt_reproject, and the history a ctx keeps for
+// mirt_render_frame_reprojected: the reprojection of csrc/reproject.h on the
+// device, byte for byte what mirt_reproject_host gives.
+//
+// One thread per pixel, 64 x 4 pixels per workgroup with the lanes of a wave
+// along x: the pixel's own rgba, t and sphere are loaded together, the hit
+// point is carried to the previous camera, and the taps' records (16 B), t and
+// sphere (4 B each) are loaded before any is used. Neighbouring lanes reproject
+// to neighbouring previous pixels, so the gathers coalesce for any coherent
+// motion. A tap's position is data: it is compared with the image as floats
+// and becomes an index only when inside (a tap outside reads the pixel's own
+// index and is dropped), so whatever t holds no access leaves the buffers.
+// The counts of mirt_history_stats are one ballot and popcount per wave and
+// kind and one vector atomic add per wave into a three-word device record.
+// No loop, no workgroup waits on another.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <new>
+
+#include "device_util.h"
+#include "internal.h"
+#include "reproject.h"
+
+#pragma clang fp contract(off)
+
+namespace mirt {
+
+// The history of mirt_render_frame_reprojected: a ping-pong pair of records
+// and planes, the display, and the counts, in one allocation that only grows.
+//   [counts: kHead bytes][records 0][records 1][t 0][sphere 0][t 1][sphere 1][display]
+struct ReprojectState {
+    void* d = nullptr;
+    size_t cap = 0;
+    bool valid = false;       // half `cur` holds the previous call's frame
+    int cur = 0;
+    int width = 0, height = 0;
+    uint64_t scene_id = 0, frames = 0;
+    mirt_camera cam{};        // the previous call's
+};
+
+void reproject_state_free(ReprojectState* st)
+{
+    if (!st) return;
+    if (st->d) (void)hipFree(st->d);
+    delete st;
+}
+
+}  // namespace mirt
+
+namespace {
+
+using namespace mirt;
+
+constexpr int kBlock = 256;
+constexpr int kTileW = 64, kTileH = 4;   // a wave per row of 64 pixels
+constexpr size_t kHead = 256;            // the counts, and the records' alignment
+
+struct ReprojectArgs {
+    ReprojectCam cur, prev;
+    int has_prev;
+    int width, height, tiles_x;
+    int max_history;
+    float t_tolerance;
+    const uint32_t* rgba;   // (may be `out`: a thread reads its pixel before it writes it)
+    const float* t;
+    const int32_t* sphere;
+    const mirt_history_px* hist;
+    const float* t_prev;
+    const int32_t* sphere_prev;
+    mirt_history_px* hist_out;
+    uint32_t* out;
+    float* out_rgb;
+    uint32_t* counts;       // [kReprojectSky, kReprojectFresh, kReprojectReused], or null
+};
+
+struct GlobalAt {
+    const mirt_history_px* h;
+    const float* tp;
+    const int32_t* sp;
+    __device__ mirt_history_px hist(size_t q) const { return h[q]; }
+    __device__ float t(size_t q) const { return tp[q]; }
+    __device__ int32_t sphere(size_t q) const { return sp[q]; }
+};
+
+template <int TAPS>
+__global__ void __launch_bounds__(kBlock) reproject_kernel(const ReprojectArgs a)
+{
+    const int bx = (int)(blockIdx.x % (unsigned)a.tiles_x), by = (int)(blockIdx.x / (unsigned)a.tiles_x);
+    const int x = bx * kTileW + (int)(threadIdx.x % kTileW), y = by * kTileH + (int)(threadIdx.x / kTileW);
+    int kind = -1;   // (a lane outside the image counts as nothing; it stays for the ballots)
+    if (x < a.width && y < a.height) {
+        const size_t i = (size_t)y * a.width + x;
+        const uint32_t px = a.rgba[i];
+        float t = a.t[i];
+        const int32_t s = a.sphere[i];
+        // (t is used by hit pixels only; kept out of their branch so that the three loads are issued together)
+        asm volatile("" : "+v"(t));
+        const GlobalAt at{a.hist, a.t_prev, a.sphere_prev};
+        const mirt_history_px h = reproject_pixel<TAPS>(a.cur, a.prev, a.has_prev != 0, at, a.width, x, y, px, t, s,
+                                                        a.max_history, a.t_tolerance, &kind);
+        a.hist_out[i] = h;
+        if (a.out_rgb) {
+            a.out_rgb[3 * i] = h.r;
+            a.out_rgb[3 * i + 1] = h.g;
+            a.out_rgb[3 * i + 2] = h.b;
+        }
+        if (a.out) a.out[i] = reproject_display(h);
+    }
+    if (!a.counts) return;   // (uniform)
+    const bool first = (threadIdx.x & 63u) == 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const unsigned long long m = __ballot(kind == k);
+        if (first && m) atomicAdd(&a.counts[k], (uint32_t)__popcll(m));
+    }
+}
+
+unsigned tile_count(int width, int height, int* tiles_x)
+{
+    // (width * height <= 2^31, so the count fits an unsigned and a grid's x)
+    const uint64_t tx = ((uint64_t)width + kTileW - 1) / kTileW, ty = ((uint64_t)height + kTileH - 1) / kTileH;
+    *tiles_x = (int)tx;
+    return (unsigned)(tx * ty);
+}
+
+// the reprojection of VALID arguments, all in device memory, enqueued on `s`
+int reproject_enqueue(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                      const uint32_t* d_rgba, const float* d_t, const int32_t* d_sphere, const mirt_history_px* d_hist,
+                      const float* d_t_prev, const int32_t* d_sphere_prev, const mirt_reproject_params* p,
+                      mirt_history_px* d_hist_out, uint32_t* d_out, float* d_out_rgb, uint32_t* d_counts, hipStream_t s)
+{
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    if (int rc = ctx_launch_begin(c, s, false)) return rc;
+    ReprojectArgs a{};
+    a.cur = reproject_cam(cam, width, height);
+    a.has_prev = cam_prev != nullptr;
+    if (cam_prev) a.prev = reproject_cam(cam_prev, width, height);
+    a.width = width;
+    a.height = height;
+    a.max_history = p->max_history;
+    a.t_tolerance = p->t_tolerance;
+    a.rgba = d_rgba;
+    a.t = d_t;
+    a.sphere = d_sphere;
+    a.hist = d_hist;
+    a.t_prev = d_t_prev;
+    a.sphere_prev = d_sphere_prev;
+    a.hist_out = d_hist_out;
+    a.out = d_out;
+    a.out_rgb = d_out_rgb;
+    a.counts = d_counts;
+    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 3 * sizeof(uint32_t), s));
+    const unsigned g = tile_count(width, height, &a.tiles_x);
+    if (p->taps == 1)
+        reproject_kernel<1><<<g, kBlock, 0, s>>>(a);
+    else
+        reproject_kernel<4><<<g, kBlock, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return ctx_launch_end(c, s);
+}
+
+// the parts of a state's allocation for an image of n pixels
+struct Parts {
+    uint32_t* counts;
+    mirt_history_px* rec[2];
+    float* t[2];
+    int32_t* sphere[2];
+    uint32_t* display;
+};
+size_t state_bytes(size_t n) { return kHead + 2 * sizeof(mirt_history_px) * n + 4 * 4 * n + 4 * n; }
+Parts state_parts(const ReprojectState* st, size_t n)
+{
+    char* const b = (char*)st->d;
+    Parts p;
+    p.counts = (uint32_t*)b;
+    p.rec[0] = (mirt_history_px*)(b + kHead);
+    p.rec[1] = p.rec[0] + n;
+    p.t[0] = (float*)(p.rec[1] + n);
+    p.sphere[0] = (int32_t*)(p.t[0] + n);
+    p.t[1] = (float*)(p.sphere[0] + n);
+    p.sphere[1] = (int32_t*)(p.t[1] + n);
+    p.display = (uint32_t*)(p.sphere[1] + n);
+    return p;
+}
+
+}  // namespace
+
+// ---- the ctx's history (render.hip's mirt_render_frame_reprojected drives these two around its frame)
+
+int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, float** d_t, int32_t** d_sphere,
+                                const char* fn)
+{
+    ReprojectState** slot = ctx_reproject_state(c);
+    if (!*slot) *slot = new (std::nothrow) ReprojectState();
+    ReprojectState* st = *slot;
+    if (!st) {
+        set_error("%s: out of host memory", fn);
+        return MIRT_E_NOMEM;
+    }
+    if (st->valid && (st->width != width || st->height != height || st->scene_id != scene_id)) {
+        st->valid = false;
+        st->frames = 0;
+    }
+    const size_t n = (size_t)width * height, bytes = state_bytes(n);
+    if (bytes > st->cap) {
+        // (a change of size emptied the history; the calls that use the buffer are blocking: nothing of it is in flight)
+        if (st->d) (void)hipFree(st->d);
+        st->d = nullptr;
+        st->cap = 0;
+        st->valid = false;
+        st->frames = 0;
+        HIP_TRY(hipMalloc(&st->d, bytes));
+        st->cap = bytes;
+    }
+    st->width = width;
+    st->height = height;
+    st->scene_id = scene_id;
+    const Parts p = state_parts(st, n);
+    const int dst = st->valid ? st->cur ^ 1 : 0;
+    *d_t = p.t[dst];
+    *d_sphere = p.sphere[dst];
+    return MIRT_OK;
+}
+
+int mirt::reproject_frame_end(mirt_ctx* c, const mirt_camera* cam, const uint32_t* d_rgba,
+                              const mirt_reproject_params* params, const uint32_t** d_shown, hipStream_t s)
+{
+    ReprojectState* st = *ctx_reproject_state(c);
+    const Parts p = state_parts(st, (size_t)st->width * st->height);
+    const int src = st->cur, dst = st->valid ? st->cur ^ 1 : 0;
+    const bool prev = st->valid;
+    st->valid = false;   // (until the launch below is enqueued)
+    if (int rc = reproject_enqueue(c, st->width, st->height, cam, prev ? &st->cam : nullptr, d_rgba, p.t[dst],
+                                   p.sphere[dst], prev ? p.rec[src] : nullptr, prev ? p.t[src] : nullptr,
+                                   prev ? p.sphere[src] : nullptr, params, p.rec[dst], p.display, nullptr, p.counts, s))
+        return rc;
+    st->cur = dst;
+    st->valid = true;
+    st->cam = *cam;
+    st->frames = prev ? st->frames + 1 : 1;
+    *d_shown = p.display;
+    return MIRT_OK;
+}
+
+extern "C" {
+
+int mirt_reproject_device(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                          const uint32_t* d_rgba, const float* d_t, const int32_t* d_sphere,
+                          const mirt_history_px* d_hist, const float* d_t_prev, const int32_t* d_sphere_prev,
+                          const mirt_reproject_params* params, mirt_history_px* d_hist_out, uint32_t* d_out,
+                          float* d_out_rgb, void* stream)
+{
+    const char* fn = "mirt_reproject_device";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!reproject_args_valid(width, height, cam, cam_prev, d_rgba, d_t, d_sphere, d_hist, d_t_prev, d_sphere_prev,
+                              params, d_hist_out)) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    return reproject_enqueue(c, width, height, cam, cam_prev, d_rgba, d_t, d_sphere, d_hist, d_t_prev, d_sphere_prev,
+                             params, d_hist_out, d_out, d_out_rgb, nullptr, (hipStream_t)stream);
+}
+
+int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                   const mirt_rgba8* rgba, const float* t, const int32_t* sphere, const mirt_history_px* hist,
+                   const float* t_prev, const int32_t* sphere_prev, const mirt_reproject_params* params,
+                   mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb)
+{
+    const char* fn = "mirt_reproject";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!reproject_args_valid(width, height, cam, cam_prev, rgba, t, sphere, hist, t_prev, sphere_prev, params,
+                              hist_out)) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    // staging freed on the way out: the records in and out first (16 B each), then the 4-byte planes and the outputs
+    const size_t n = (size_t)width * height;
+    const size_t b_prev = hist ? n : 0, b_out = out ? 4 * n : 0, b_rgb = out_rgb ? 12 * n : 0;
+    DevMem m;
+    HIP_TRY(hipMalloc(&m.p, 16 * n + 16 * b_prev + 12 * n + 8 * b_prev + b_out + b_rgb));
+    char* const d_ho = (char*)m.p;
+    char* const d_h = d_ho + 16 * n;
+    char* const d_px = d_h + 16 * b_prev;
+    char* const d_t = d_px + 4 * n;
+    char* const d_s = d_t + 4 * n;
+    char* const d_tp = d_s + 4 * n;
+    char* const d_sp = d_tp + 4 * b_prev;
+    char* const d_o = d_sp + 4 * b_prev;
+    char* const d_rgb = d_o + b_out;
+    HIP_TRY(hipMemcpyAsync(d_px, rgba, 4 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_t, t, 4 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_s, sphere, 4 * n, hipMemcpyHostToDevice, s));
+    if (hist) {
+        HIP_TRY(hipMemcpyAsync(d_h, hist, 16 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_tp, t_prev, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_sp, sphere_prev, 4 * n, hipMemcpyHostToDevice, s));
+    }
+    const int rc = reproject_enqueue(c, width, height, cam, cam_prev, (const uint32_t*)d_px, (const float*)d_t,
+                                     (const int32_t*)d_s, hist ? (const mirt_history_px*)d_h : nullptr,
+                                     hist ? (const float*)d_tp : nullptr, hist ? (const int32_t*)d_sp : nullptr, params,
+                                     (mirt_history_px*)d_ho, out ? (uint32_t*)d_o : nullptr,
+                                     out_rgb ? (float*)d_rgb : nullptr, nullptr, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);   // the copies in still read the caller's memory and write the staging
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(hist_out, d_ho, 16 * n, hipMemcpyDeviceToHost, s));
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_o, b_out, hipMemcpyDeviceToHost, s));
+    if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, d_rgb, b_rgb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MIRT_OK;
+}
+
+int mirt_history_reset(mirt_ctx* c)
+{
+    if (!c) {
+        set_error("mirt_history_reset: null context");
+        return MIRT_E_INVALID;
+    }
+    if (ReprojectState* st = *ctx_reproject_state(c)) {
+        st->valid = false;
+        st->frames = 0;
+    }
+    return MIRT_OK;
+}
+
+int mirt_history_stats_get(mirt_ctx* c, mirt_history_stats* out)
+{
+    const char* fn = "mirt_history_stats_get";
+    if (!c || !out) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    *out = mirt_history_stats{};
+    const ReprojectState* st = *ctx_reproject_state(c);
+    if (!st) return MIRT_OK;
+    out->bytes = st->cap;
+    if (!st->valid) return MIRT_OK;
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    uint32_t counts[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, st->d, sizeof counts, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->frames = st->frames;
+    out->scene_id = st->scene_id;
+    out->width = st->width;
+    out->height = st->height;
+    out->sky = counts[kReprojectSky];
+    out->fresh = counts[kReprojectFresh];
+    out->reused = counts[kReprojectReused];
+    return MIRT_OK;
+}
+
+int mirt_history_read(mirt_ctx* c, mirt_history_px* hist, size_t n)
+{
+    const char* fn = "mirt_history_read";
+    if (!c || !hist) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    const ReprojectState* st = *ctx_reproject_state(c);
+    if (!st || !st->valid || n != (size_t)st->width * st->height) {
+        set_error("%s: no history of %zu pixels", fn, n);
+        return MIRT_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(ctx_device(c)));
+    hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
+    HIP_TRY(hipMemcpyAsync(hist, state_parts(st, n).rec[st->cur], n * sizeof *hist, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MIRT_OK;
+}
+
+}  // extern "C"

@@ -781,6 +781,91 @@ class Renderer:
                                                 ptr(out), ptr(plain)), "mirt_render_frame_denoised")
         return (out, plain) if raw else out
 
+    # ---- reprojection (a per-pixel history carried from the previous camera to the current one)
+    @staticmethod
+    def _reproject_params(params):
+        """abi.ReprojectParams from one, from (max_history, taps, t_tolerance), or the defaults for None."""
+        if isinstance(params, abi.ReprojectParams):
+            return params
+        p = abi.ReprojectParams()
+        load().mirt_reproject_params_default(C.byref(p))
+        if params is not None:
+            p.max_history, p.taps, p.t_tolerance = params
+        return p
+
+    def reproject(self, cam, rgba, t, sphere, prev=None, params=None, rgb=False, out=None, stream=None):
+        """The reprojection of mirt.h's mirt_reproject_params on a frame given
+        as numpy arrays (mirt_reproject: blocking) or as torch tensors on the
+        ctx's device (mirt_reproject_device: enqueued on `stream`, an integer
+        hipStream_t, 0 / None = the default stream, not waited for). rgba:
+        (H, W, 4) uint8; t: (H, W) float32; sphere: (H, W) int32; prev: None on
+        the first frame, else (cam_prev, hist, t_prev, sphere_prev) with hist
+        (H, W) abi.HISTORY records (tensors: (H, W, 4) float32 holding the same
+        16 bytes). Returns (hist_out, display), or with rgb=True (hist_out,
+        display, (H, W, 3) float32). `out` (device form): the uint8 tensor the
+        display goes to, which may be `rgba` itself."""
+        p = self._reproject_params(params)
+        h, w = sphere.shape
+        cam_prev, hist, t_prev, sphere_prev = prev if prev is not None else (None, None, None, None)
+        cp = C.byref(cam_prev) if cam_prev is not None else None
+        if not isinstance(sphere, np.ndarray):   # device tensors
+            import torch
+            for a, dtype in ((rgba, torch.uint8), (t, torch.float32), (sphere, torch.int32), (hist, torch.float32),
+                             (t_prev, torch.float32), (sphere_prev, torch.int32), (out, torch.uint8)):
+                if a is not None and not (a.is_cuda and a.is_contiguous() and a.dtype == dtype):
+                    raise MirtError("reproject: tensors must be contiguous, on the device, uint8 / float32 / int32")
+            hist_out = torch.empty((h, w, 4), dtype=torch.float32, device=sphere.device)
+            if out is None:
+                out = torch.empty((h, w, 4), dtype=torch.uint8, device=sphere.device)
+            out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=sphere.device) if rgb else None
+            dp = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+            check(self.L.mirt_reproject_device(self.h, w, h, C.byref(cam), cp, dp(rgba), dp(t), dp(sphere), dp(hist),
+                                               dp(t_prev), dp(sphere_prev), C.byref(p), dp(hist_out), dp(out),
+                                               dp(out_rgb), C.c_void_p(stream or 0)), "mirt_reproject_device")
+            return (hist_out, out, out_rgb) if rgb else (hist_out, out)
+        cont = lambda a, dtype: None if a is None else np.ascontiguousarray(a, dtype)   # noqa: E731
+        rgba, t, sphere = cont(rgba, np.uint8), cont(t, np.float32), cont(sphere, np.int32)
+        hist, t_prev, sphere_prev = cont(hist, abi.HISTORY), cont(t_prev, np.float32), cont(sphere_prev, np.int32)
+        hist_out = np.zeros((h, w), abi.HISTORY)
+        res = np.zeros((h, w, 4), np.uint8)
+        out_rgb = np.zeros((h, w, 3), np.float32) if rgb else None
+        check(self.L.mirt_reproject(self.h, w, h, C.byref(cam), cp, ptr(rgba), ptr(t), ptr(sphere), ptr(hist),
+                                    ptr(t_prev), ptr(sphere_prev), C.byref(p), ptr(hist_out), ptr(res), ptr(out_rgb)),
+              "mirt_reproject")
+        return (hist_out, res, out_rgb) if rgb else (hist_out, res)
+
+    def render_frame_reprojected(self, cam, width, height, params=None, raw=False, **frame_desc_args):
+        """render_frame (frame_desc's keyword arguments; one sample, one shard,
+        no jitter, not accumulating) and the display of its history
+        (mirt_render_frame_reprojected): each pixel's record is carried from
+        where the previous call's camera saw the same surface. Returns the
+        (height, width, 4) uint8 display, or with raw=True (display, the
+        one-sample display render_frame returns)."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        out = np.zeros((height, width, 4), np.uint8)
+        plain = np.zeros((height, width, 4), np.uint8) if raw else None
+        check(self.L.mirt_render_frame_reprojected(self.h, C.byref(cam), C.byref(fd),
+                                                   C.byref(self._reproject_params(params)), ptr(out), ptr(plain)),
+              "mirt_render_frame_reprojected")
+        return (out, plain) if raw else out
+
+    def history_reset(self):
+        """Empty the history of render_frame_reprojected (mirt_history_reset)."""
+        check(self.L.mirt_history_reset(self.h), "mirt_history_reset")
+
+    def history_stats(self):
+        """mirt_history_stats as a dict (waits for the ctx's stream)."""
+        st = abi.HistoryStats()
+        check(self.L.mirt_history_stats_get(self.h, C.byref(st)), "mirt_history_stats_get")
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def history_read(self):
+        """The current records, (height, width) abi.HISTORY (mirt_history_read)."""
+        st = self.history_stats()
+        out = np.zeros((st["height"], st["width"]), abi.HISTORY)
+        check(self.L.mirt_history_read(self.h, ptr(out), out.size), "mirt_history_read")
+        return out
+
     def share_accum(self, owner):
         """Use `owner`'s accumulation buffer (mirt_ctx_share_accum): the ctxs
         of one accumulating display loop with frames in flight; None: a

@@ -762,6 +762,119 @@ int mirt_render_frame_denoised(mirt_ctx *ctx, const mirt_camera *cam, const mirt
                                const mirt_frame_desc *fd, const mirt_denoise_params *params, mirt_rgba8 *out,
                                mirt_rgba8 *raw);
 
+/* Reprojecting a frame's history when the camera moves. The accumulating loop
+   (main.c:379-408) converges only while the camera stands still: every move
+   starts over at one sample (main.c:350-377). Here each pixel keeps a record
+   of its own -- the mean of n samples -- and a new one-sample frame takes the
+   record of the surface it shows from wherever the previous camera saw that
+   surface, found by reprojecting the pixel's primary hit point. The definition
+   (csrc/reproject.h; every operation one correctly rounded binary32 operation,
+   in this order), for an unsharded image of width x height pixels, row-major,
+   pixel i = y * width + x:
+     cameras: cam, and cam_prev of the previous frame; of each the constants of
+       a frame (ray.c:18-24): p, forward, right, up, sw = 2 half_w,
+       sh = 2 half_h, hor = right * sw, ver = up * sh, aspect, wf, hf;
+     current frame: rgba (a one-sample frame's display), t and sphere
+       (mirt_primary_planes); previous frame: hist (mirt_history_px: the mean
+       of n samples, n == 0 = none), t_prev, sphere_prev. cam_prev, hist,
+       t_prev and sphere_prev are NULL together on the first frame: every
+       pixel then takes "no history";
+     1 c[ch] = (float)u8 / 255.0f; s = sphere[i]; s < 0: no history;
+     2 d = the unjittered pinhole direction of (x, y) under cam (main.c:362-365,
+       ray.c:26-31, normalised; zero for a zero length); X = p + d * t[i];
+     3 e = X - p_prev; zf = dot(e, forward_prev), left to right;
+       !(zf > 0): no history;
+     4 a = dot(e, right_prev) / zf; b = dot(e, up_prev) / zf; u = a / sw_prev;
+       v = b / sh_prev; xf = (u / aspect + 0.5f) * wf; yf = (0.5f - v) * hf;
+     5 l = sqrtf(dot(e, e));
+     6 taps == 1: the tap (floorf(xf + 0.5f), floorf(yf + 0.5f)), w = 1;
+       taps == 4: gx = floorf(xf), gy = floorf(yf), ax = xf - gx, ay = yf - gy,
+       the taps (gx, gy), (gx + 1, gy), (gx, gy + 1), (gx + 1, gy + 1) in this
+       order with w = (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay;
+     7 a tap (tx, ty), kept as floats, is inside iff tx >= 0 && tx < wf &&
+       ty >= 0 && ty < hf, and only then becomes an index: a t of NaN, infinity
+       or 1e38 never gives an access outside the image;
+     8 an inside tap q is valid iff w > 0, sphere_prev[q] == s, hist[q].n >= 1
+       and fabsf(l - t_prev[q]) <= t_tolerance * l;
+     9 over the valid taps in order, from +0.0f: sw_ = sw_ + w,
+       sc[ch] = sc[ch] + hist[q].c[ch] * w, nmin = min n; none valid: no
+       history; else m[ch] = sc[ch] / sw_;
+    10 n_new = min(nmin + 1, max_history),
+       mean[ch] = m[ch] + (c[ch] - m[ch]) / (float)n_new; no history: n_new = 1,
+       mean = c;
+    11 hist_out[i] = {mean, n_new} (required; must not be hist); out (may be
+       NULL): RGBA8 of mean by the denoiser's cast, alpha 255; out_rgb (may be
+       NULL): mean's three floats -- what mirt_denoise_device takes as accum
+       with frames = 1.
+   MIRT_E_INVALID, before any device call: NULL ctx (not mirt_reproject_host),
+   params, cam, rgba, t, sphere or hist_out; some but not all of cam_prev,
+   hist, t_prev, sphere_prev; hist_out == hist; width or height < 1 or
+   width * height beyond 2^31; max_history outside 1..65536; taps not 1 or 4;
+   t_tolerance negative or not finite.
+   mirt_reproject_host: on the host (no device call, no ctx).
+   mirt_reproject_device: everything in device memory; enqueued on `stream`
+   (NULL: the default stream), returns without waiting; byte for byte the host
+   form's result. A launch on another stream than the ctx's previous launch
+   first waits for that one, as frames and the denoiser do. d_out may alias
+   d_rgba.
+   mirt_reproject: blocking, host pointers.
+   mirt_render_frame_reprojected: the moving-camera loop in one blocking call.
+   Renders exactly what mirt_render_frame_planes renders (colours and
+   accumulation buffer byte for byte the plain call's), t and sphere into
+   buffers the ctx keeps, then reprojects from the ctx's history -- the
+   previous call's camera, planes and records -- into the other half of a
+   ping-pong pair, which becomes the history. `out` receives the display,
+   `raw` (may be NULL) the one-sample display. The history starts empty after
+   mirt_history_reset, a change of width or height, a change of
+   mirt_ctx_scene_id (every install: sphere indices and positions may have
+   changed) and mirt_create. In addition MIRT_E_INVALID, before any device
+   call, for a NULL fd or out, an invalid fd, fd->accumulate != 0,
+   fd->samples > 1, fd->num_shards != 1, fd->jitter != 0, fd->max_depth < 1, or
+   a ctx in a mirt_ctx_share_accum chain. Under MIRT_OPT_PRIMARY_CACHE the
+   frame is the BYPASS (PLANES) any planes frame is.
+   mirt_history_stats_get: waits for the ctx's stream. mirt_history_read: the
+   current records, n = width * height of them (MIRT_E_INVALID without a
+   history or for another n).
+   Lens and jittered frames (their primary ray is not the pinhole's), shards,
+   mirt_multi, frames in flight and moving spheres are out of scope. */
+typedef struct mirt_history_px {
+    float r, g, b;   /* the mean of n samples */
+    int32_t n;       /* 0 = no history */
+} mirt_history_px;   /* 16 B */
+typedef struct mirt_reproject_params {
+    int32_t max_history;   /* 1..65536: a record's n stops growing here */
+    int32_t taps;          /* 1 = the nearest previous pixel, 4 = bilinear */
+    float t_tolerance;     /* >= 0: a tap's stored distance may differ by this share of l */
+} mirt_reproject_params;
+typedef struct mirt_history_stats {
+    uint64_t frames;     /* mirt_render_frame_reprojected calls since the history was last empty */
+    uint64_t scene_id;   /* mirt_ctx_scene_id of the history (0: none) */
+    uint64_t bytes;      /* device memory held for the history */
+    uint64_t reused;     /* the last call's pixels with n_new > 1 */
+    uint64_t fresh;      /* its hit pixels with n_new == 1 */
+    uint64_t sky;        /* its pixels with sphere < 0 */
+    int32_t width, height;   /* of the history (0: none) */
+} mirt_history_stats;    /* 56 B */
+void mirt_reproject_params_default(mirt_reproject_params *out);   /* 64, 4, 1/64 */
+int mirt_reproject_host(int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                        const mirt_rgba8 *rgba, const float *t, const int32_t *sphere, const mirt_history_px *hist,
+                        const float *t_prev, const int32_t *sphere_prev, const mirt_reproject_params *params,
+                        mirt_history_px *hist_out, mirt_rgba8 *out, float *out_rgb);
+int mirt_reproject_device(mirt_ctx *ctx, int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                          const uint32_t *d_rgba, const float *d_t, const int32_t *d_sphere,
+                          const mirt_history_px *d_hist, const float *d_t_prev, const int32_t *d_sphere_prev,
+                          const mirt_reproject_params *params, mirt_history_px *d_hist_out, uint32_t *d_out,
+                          float *d_out_rgb, void *stream);
+int mirt_reproject(mirt_ctx *ctx, int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                   const mirt_rgba8 *rgba, const float *t, const int32_t *sphere, const mirt_history_px *hist,
+                   const float *t_prev, const int32_t *sphere_prev, const mirt_reproject_params *params,
+                   mirt_history_px *hist_out, mirt_rgba8 *out, float *out_rgb);
+int mirt_render_frame_reprojected(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd,
+                                  const mirt_reproject_params *params, mirt_rgba8 *out, mirt_rgba8 *raw);
+int mirt_history_reset(mirt_ctx *ctx);
+int mirt_history_stats_get(mirt_ctx *ctx, mirt_history_stats *out);
+int mirt_history_read(mirt_ctx *ctx, mirt_history_px *hist, size_t n);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
