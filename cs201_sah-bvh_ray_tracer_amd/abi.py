@@ -122,6 +122,18 @@ class HistoryStats(C.Structure):
                 ("fresh", C.c_uint64), ("sky", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class SphereMotion(C.Structure):
+    """mirt_sphere_motion: geo[num_spheres] and geo_prev[num_prev] float4 (centre, radius), prev_index (or NULL)"""
+    _fields_ = [("geo", C.c_void_p), ("geo_prev", C.c_void_p), ("prev_index", C.c_void_p),
+                ("num_spheres", C.c_int32), ("num_prev", C.c_int32)]
+
+
+class HistoryMotion(C.Structure):
+    """mirt_history_motion"""
+    _fields_ = [("from_scene_id", C.c_uint64), ("to_scene_id", C.c_uint64), ("bytes", C.c_uint64),
+                ("rebuilt", C.c_int32), ("carried", C.c_int32)]
+
+
 # mirt_history_px: the mean of n samples (n == 0: no history)
 HISTORY = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("n", np.int32)])
 assert HISTORY.itemsize == 16
@@ -283,6 +295,10 @@ SIGNATURES = [
     ("mirt_history_reset", I, [P]),
     ("mirt_history_stats_get", I, [P, P]),
     ("mirt_history_read", I, [P, P, C.c_size_t]),
+    ("mirt_reproject_motion_host", I, [I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject_motion_device", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject_motion", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_history_motion_get", I, [P, P]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),
@@ -365,6 +381,7 @@ OPT_CONFIRM_ONCE, OPT_DEBUG_FAIL_CONFIRM = 21, 22
 OPT_BUILD_FINISH = 23     # the device build's finish: 0 never, 1 automatic (default), 2..64 = F
 OPT_PRIMARY_CACHE = 24    # a still camera's frames start from the stored primary hits: 0 off (default), 1 on
 OPT_DENOISE_TILE = 26     # mirt_denoise*: passes of spacing 1 and 2 from an LDS tile with halo (1) or by direct loads (0)
+OPT_HISTORY_MOTION = 27   # refits / updates record a link, reprojected frames carry their history over it: 0 off (default), 1 on
 # mirt_primary_cache_stats: `last` (how the last frame met the cache) and `reason` (why it was no hit)
 PCACHE_BYPASS, PCACHE_FILL, PCACHE_HIT = 0, 1, 2
 PCACHE_KIND = {PCACHE_BYPASS: "bypass", PCACHE_FILL: "fill", PCACHE_HIT: "hit"}

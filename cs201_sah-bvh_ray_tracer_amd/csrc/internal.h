@@ -139,10 +139,25 @@ bool reproject_args_valid(int width, int height, const void* cam, const void* ca
 struct ReprojectState;
 ReprojectState** ctx_reproject_state(mirt_ctx* c);
 void reproject_state_free(ReprojectState* st);
-int reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, float** d_t, int32_t** d_sphere,
-                          const char* fn);
+// link_from / link_motion (MIRT_OPT_HISTORY_MOTION 1): the scene id the slot's
+// link to `scene_id` starts at (0: no link the ctx may use) and that link's
+// motion, device pointers. A history of exactly the scene link_from is kept
+// by begin, and end reprojects it with the motion; reproject_last_carried:
+// the last frame did.
+int reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, uint64_t link_from, float** d_t,
+                          int32_t** d_sphere, const char* fn);
 int reproject_frame_end(mirt_ctx* c, const mirt_camera* cam, const uint32_t* d_rgba,
-                        const mirt_reproject_params* params, const uint32_t** d_shown, ihipStream_t* stream);
+                        const mirt_reproject_params* params, const mirt_sphere_motion* link_motion,
+                        const uint32_t** d_shown, ihipStream_t* stream);
+bool reproject_last_carried(mirt_ctx* c);
+// render.hip: what the install a refit or an update is about to make records
+// on the scene slot when the ctx has MIRT_OPT_HISTORY_MOTION 1:
+// active, whether it is a rebuild, and the rebuild's permutation (perm[i] = the
+// previous index of the sphere now at i) in device memory, written on the
+// ctx's stream, or in host memory. Holds until ctx_link_intent_clear; an
+// install outside such a bracket clears the slot's link.
+void ctx_link_intent(mirt_ctx* c, bool rebuilt, const int32_t* d_perm, const int32_t* h_perm);
+void ctx_link_intent_clear(mirt_ctx* c);
 // render.hip: a launch on `stream` that uses scratch the ctx keeps, outside a
 // frame. begin: the stream waits for the ctx's previous launch if that ran on
 // another stream (host_wait: the host does, whichever stream it ran on --

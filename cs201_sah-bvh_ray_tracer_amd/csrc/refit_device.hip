@@ -285,6 +285,15 @@ int host_refit(hipStream_t s, const ResidentScene& rs, const mirt_sphere** spher
     return mirt_bvh_refit_flat(nodes.data(), nn, *spheres, ns, end);
 }
 
+// The installs a refit or an update makes between here and the scope's end are ones a history can be carried over
+// (MIRT_OPT_HISTORY_MOTION, ctx_link_intent): every path of both calls, the declined inputs' host uploads included.
+struct LinkIntent {
+    mirt_ctx* c;
+    explicit LinkIntent(mirt_ctx* ctx) : c(ctx) { ctx_link_intent(c, false, nullptr, nullptr); }
+    ~LinkIntent() { ctx_link_intent_clear(c); }
+    void rebuild(const int32_t* d_perm, const int32_t* h_perm) { ctx_link_intent(c, true, d_perm, h_perm); }
+};
+
 // exactly one of `spheres` (host) and `d_spheres` (device) is set, unless ns == 0
 int refit(mirt_ctx* c, const mirt_sphere* spheres, const void* d_spheres, int ns, int end, mirt_node* out_nodes,
           const char* fn)
@@ -292,6 +301,7 @@ try {
     ResidentScene rs{};
     if (int rc = resident_scene(c, ns >= 0 && (ns == 0 || spheres || d_spheres) && end >= 0 && end <= ns, ns, &rs, fn))
         return rc;
+    LinkIntent link(c);
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point t) {
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -366,6 +376,7 @@ try {
     const bool args_ok = ns >= 0 && (ns == 0 || spheres || d_spheres) && start >= 0 && end >= start && end <= ns &&
                          !(d_reordered && d_reordered == d_spheres);
     if (int rc = resident_scene(c, args_ok, ns, &rs, fn)) return rc;
+    LinkIntent link(c);
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx_device(c)));
     hipStream_t s = (hipStream_t)mirt_ctx_stream(c);
@@ -439,6 +450,7 @@ try {
                                                                                d_perm);
                     e = hipGetLastError();
                 }
+                link.rebuild(d_perm, nullptr);   // (written by perm_kernel on `s`, ahead of the install's copy of it)
                 mirt_tree_quality qb;
                 if (e == hipSuccess) rc = quality_device(s, built.nodes, built.num_nodes, ns, &qb, fn);
                 if (e == hipSuccess && !rc) rc = layout_device(c, s, built.aos, ns, built.nodes, built.num_nodes, fn);
@@ -490,6 +502,7 @@ try {
             }
             mirt_tree_quality qb;
             int rc = mirt_bvh_quality_flat(bn, bcount, ns, &qb);
+            link.rebuild(nullptr, from.data());
             if (!rc) rc = mirt_scene_upload_flat(c, copy.data(), ns, bn, bcount);
             mirt_bvh_free_flat(bn);
             if (rc) return rc;

@@ -1862,12 +1862,42 @@ struct Scene {
 // An install through any member replaces `cur` for all of them; the replaced
 // scene waits in `retired` until its readers' events have passed (checked at
 // the slot's later installs, waited for when the slot itself goes).
+// The link of a scene slot (MIRT_OPT_HISTORY_MOTION): what a
+// history of the scene `from` needs to be carried to the scene `to` that a
+// refit or an update installed over it. One allocation of two halves, each
+// [Geo4 x n: the replaced scene's geo][int32 x n: the rebuild's permutation];
+// an install stages into the half that is not the link and the commit flips,
+// so a failed install leaves the link as it was. The allocation only grows
+// and goes with the slot: no hipFree per install (MEASUREMENTS.md E).
+// No event: the only reader is mirt_render_frame_reprojected, a blocking call
+// that has waited for its kernel when it returns, and the only writers are
+// installs, blocking calls too that wait for their copies before they return
+// -- all of them made by the group's one host thread, so a write never meets
+// a read in flight, whichever member's stream either ran on.
+struct HistoryLink {
+    void* d = nullptr;
+    size_t cap = 0;             // of both halves together
+    int half = 0;               // the half the link reads
+    bool valid = false;
+    uint64_t from = 0, to = 0;
+    int n = 0;                  // spheres of `from` (and of `to`: refits and updates keep the count)
+    bool rebuilt = false;       // the half holds a permutation
+    bool staged = false;        // the other half holds the install in progress: staged_from, staged_n, staged_rebuilt
+    uint64_t staged_from = 0;
+    int staged_n = 0;
+    bool staged_rebuilt = false;
+    char* base(int h) const { return (char*)d + (size_t)h * (cap / 2); }
+    const float* geo_prev(int h) const { return (const float*)base(h); }
+    const int32_t* perm(int h) const { return (const int32_t*)(base(h) + sizeof(float4) * (size_t)n); }
+};
+
 struct SceneSlot {
     Scene* cur = nullptr;
     std::vector<mirt_ctx*> members;
     std::vector<Scene*> retired;
     double base_cost = 0.0;     // mirt_scene_update_device: the cost of the tree it last installed
     bool have_base_cost = false;  // dropped by every install of a scene
+    HistoryLink link;           // set by a refit / update of an option-1 ctx, cleared by every other install
 };
 
 // What the camera rays of a frame and its pixel -> row map are computed from:
@@ -1980,6 +2010,10 @@ struct mirt_ctx {
     void* d_guides = nullptr;   // mirt_render_frame_denoised: the frame's sphere and normal planes
     size_t guides_cap = 0;
     mirt::ReprojectState* reproject = nullptr;  // mirt_render_frame_reprojected's history (reproject.hip)
+    int history_motion = 0;     // MIRT_OPT_HISTORY_MOTION: installs record a link, reprojected frames carry over it
+    // the install a refit / update is about to make (ctx_link_intent): what its link holds
+    bool link_intent = false, link_rebuilt = false;
+    const int32_t *link_d_perm = nullptr, *link_h_perm = nullptr;
 };
 
 namespace {
@@ -2085,6 +2119,7 @@ void slot_leave(mirt_ctx* c)
     if (!sl->members.empty()) return;
     slot_drop_scene(sl);
     slot_reap(sl, true);
+    if (sl->link.d) (void)hipFree(sl->link.d);
     delete sl;
 }
 
@@ -2096,8 +2131,53 @@ uint64_t next_scene_id()
     return ++last;
 }
 
+// Before an install gives up the slot's scene: when the ctx has
+// MIRT_OPT_HISTORY_MOTION 1 and the install is a refit's or an update's
+// (ctx_link_intent), the resident scene's geo array and the rebuild's
+// permutation are copied into the link's free half and waited for -- the
+// scene may be freed by the install itself. Nothing of the link proper
+// changes here; slot_install commits or clears it. With the option at 0, or
+// outside a refit / update, no device call is made.
+int link_stage(mirt_ctx* c)
+{
+    SceneSlot* sl = c->slot;
+    HistoryLink& lk = sl->link;
+    lk.staged = false;
+    const Scene* sn = sl->cur;
+    if (c->history_motion != 1 || !c->link_intent || !sn || sn->num_spheres < 1) return MIRT_OK;
+    const size_t n = (size_t)sn->num_spheres;
+    const size_t half = ((sizeof(float4) + sizeof(int32_t)) * n + 255) & ~(size_t)255;
+    if (2 * half > lk.cap) {
+        // (a link in force holds as many spheres as the resident scene: it fits, and is not lost here)
+        void* d = nullptr;
+        HIP_TRY(hipMalloc(&d, 2 * half));
+        if (lk.d) (void)hipFree(lk.d);
+        lk.d = d;
+        lk.cap = 2 * half;
+        lk.valid = false;
+    }
+    const int h = lk.half ^ 1;   // (slot_install flips)
+    char* const dst = lk.base(h);
+    HIP_TRY(hipMemcpyAsync(dst, sn->d_geo, sizeof(float4) * n, hipMemcpyDeviceToDevice, c->stream));
+    if (c->link_rebuilt) {
+        if (c->link_d_perm)
+            HIP_TRY(hipMemcpyAsync(dst + sizeof(float4) * n, c->link_d_perm, sizeof(int32_t) * n,
+                                   hipMemcpyDeviceToDevice, c->stream));
+        else
+            HIP_TRY(hipMemcpyAsync(dst + sizeof(float4) * n, c->link_h_perm, sizeof(int32_t) * n,
+                                   hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    lk.staged = true;
+    lk.staged_from = sn->id;
+    lk.staged_n = sn->num_spheres;
+    lk.staged_rebuilt = c->link_rebuilt;
+    return MIRT_OK;
+}
+
 // `sn` (complete on the device, refs == 0) becomes the scene of the ctx's
-// slot, for every member.
+// slot, for every member. The link link_stage staged for this install comes
+// into force; any other install clears the slot's link.
 void slot_install(mirt_ctx* c, Scene* sn)
 {
     SceneSlot* sl = c->slot;
@@ -2106,6 +2186,18 @@ void slot_install(mirt_ctx* c, Scene* sn)
     sn->id = next_scene_id();
     sn->refs = 1;
     sl->cur = sn;
+    HistoryLink& lk = sl->link;
+    if (lk.staged && lk.staged_n == sn->num_spheres) {
+        lk.half ^= 1;
+        lk.valid = true;
+        lk.from = lk.staged_from;
+        lk.to = sn->id;
+        lk.n = lk.staged_n;
+        lk.rebuilt = lk.staged_rebuilt;
+    } else {
+        lk.valid = false;
+    }
+    lk.staged = false;
 }
 
 // MIRT_OPT_CONFIRM_ONCE in effect for the uploaded scene. Automatic (2): on up
@@ -2796,6 +2888,10 @@ try {
         {(void**)&sn->d_leaves, 0, lay.leaf_box_off, lay.leaf_box.data(), sizeof(LeafBox) * nl},
         {(void**)&sn->d_ndepth, lay.ndepth.size(), 0, lay.ndepth.data(), lay.ndepth.size()},
     };
+    if (int rc = link_stage(c)) {
+        scene_free(sn);
+        return rc;
+    }
     // the slot gives up the scene it held first, as this call always has: until
     // every array is in place ctx_ok rejects the slot's contexts
     slot_drop_scene(c->slot);
@@ -3051,6 +3147,18 @@ BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 DenoiseState** ctx_denoise_state(mirt_ctx* c) { return &c->denoise; }
 int ctx_denoise_tile(const mirt_ctx* c) { return c->denoise_tile; }
 ReprojectState** ctx_reproject_state(mirt_ctx* c) { return &c->reproject; }
+void ctx_link_intent(mirt_ctx* c, bool rebuilt, const int32_t* d_perm, const int32_t* h_perm)
+{
+    c->link_intent = true;
+    c->link_rebuilt = rebuilt;
+    c->link_d_perm = d_perm;
+    c->link_h_perm = h_perm;
+}
+void ctx_link_intent_clear(mirt_ctx* c)
+{
+    c->link_intent = c->link_rebuilt = false;
+    c->link_d_perm = c->link_h_perm = nullptr;
+}
 int ctx_launch_begin(mirt_ctx* c, hipStream_t s, bool host_wait)
 {
     if (c->launched && host_wait) HIP_TRY(hipEventSynchronize(c->done));
@@ -3093,6 +3201,10 @@ int ctx_install_scene(mirt_ctx* c, const DeviceScene& sc)
     sn->c_max = sc.c_max;
     sn->o_bound = sc.o_bound;
     sn->num_spheres = sc.num_spheres;
+    if (int rc = link_stage(c)) {
+        delete sn;   // (the arrays stay the caller's)
+        return rc;
+    }
     slot_install(c, sn);
     return MIRT_OK;
 }
@@ -3551,7 +3663,14 @@ int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mir
     if (!ctx_ok(c, true, fn)) return MIRT_E_NOSCENE;
     float* d_t = nullptr;
     int32_t* d_sphere = nullptr;
-    if (int rc = reproject_frame_begin(c, fd->width, fd->height, scene_of(c)->id, &d_t, &d_sphere, fn)) return rc;
+    // the slot's link, if this ctx may use it and it ends at the resident scene (reproject_frame_begin decides by its start)
+    const Scene* sn = scene_of(c);
+    const HistoryLink& lk = c->slot->link;
+    const bool linked = c->history_motion == 1 && lk.valid && lk.to == sn->id && lk.n == sn->num_spheres;
+    const mirt_sphere_motion motion{(const float*)sn->d_geo, linked ? lk.geo_prev(lk.half) : nullptr,
+                                    linked && lk.rebuilt ? lk.perm(lk.half) : nullptr, sn->num_spheres, lk.n};
+    if (int rc = reproject_frame_begin(c, fd->width, fd->height, sn->id, linked ? lk.from : 0, &d_t, &d_sphere, fn))
+        return rc;
     c->planes = Planes{d_t, d_sphere, nullptr};
     c->lone_frame = true;
     uint32_t* disp = nullptr;
@@ -3560,7 +3679,7 @@ int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mir
     c->planes = Planes{};
     if (rc) return rc;
     const uint32_t* shown = nullptr;
-    rc = reproject_frame_end(c, cam, disp, params, &shown, c->stream);
+    rc = reproject_frame_end(c, cam, disp, params, linked ? &motion : nullptr, &shown, c->stream);
     if (rc) return rc;
     const size_t row = (size_t)fd->width * 4;   // copies out as enqueue_host_frame's: rows x width
     if (raw) HIP_TRY(hipMemcpy2DAsync(raw, row, disp, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
@@ -3707,6 +3826,24 @@ try {
 } catch (const std::bad_alloc&) {
     set_error("mirt_ctx_share_scene: out of host memory");
     return MIRT_E_NOMEM;
+}
+
+int mirt_history_motion_get(mirt_ctx* c, mirt_history_motion* out)
+{
+    if (!c || !out) {
+        set_error("mirt_history_motion_get: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    *out = mirt_history_motion{};
+    const HistoryLink& lk = c->slot->link;
+    out->bytes = lk.cap;
+    if (lk.valid) {
+        out->from_scene_id = lk.from;
+        out->to_scene_id = lk.to;
+        out->rebuilt = lk.rebuilt ? 1 : 0;
+    }
+    out->carried = reproject_last_carried(c) ? 1 : 0;
+    return MIRT_OK;
 }
 
 uint64_t mirt_ctx_scene_id(mirt_ctx* c)
@@ -4261,6 +4398,10 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         if (value != 0 && value != 1) break;
         c->denoise_tile = value;
         return MIRT_OK;
+    case MIRT_OPT_HISTORY_MOTION:
+        if (value != 0 && value != 1) break;
+        c->history_motion = value;
+        return MIRT_OK;
     case MIRT_OPT_PRIMARY_CACHE:
         if (value != 0 && value != 1) break;
         if (value == 0 && c->pc.d) {
@@ -4302,6 +4443,7 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_BUILD_FINISH) return c->build_finish;
     if (option == MIRT_OPT_PRIMARY_CACHE) return c->pc.on;
     if (option == MIRT_OPT_DENOISE_TILE) return c->denoise_tile;
+    if (option == MIRT_OPT_HISTORY_MOTION) return c->history_motion;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
     set_error("mirt_get_option: bad option %d", option);
     return MIRT_E_INVALID;

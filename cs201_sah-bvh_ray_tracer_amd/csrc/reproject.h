@@ -48,6 +48,29 @@
 //
 // Unlike the denoiser's, the tap positions depend on the data; step 7 is what
 // keeps every access inside the image whatever t holds.
+//
+// With a MOTION (mirt_reproject_motion*, mirt_sphere_motion: the spheres moved
+// between the two frames) the hit point is first carried back to where its
+// sphere was. geo[num_spheres] is the scene `sphere` indexes, geo_prev[num_prev]
+// the previous frame's, each {centre.xyz, radius}; prev_index[s] is the index in
+// geo_prev of the sphere that is now s (none: the identity). Steps 2, 3 and 8
+// become:
+//
+//  2  as above, X[j] = p[j] + d[j] * t[i].
+//  2a s is data: !(0 <= s < num_spheres): no history. sp = prev_index ?
+//     prev_index[s] : s; !(0 <= sp < num_prev): no history. Both comparisons
+//     are made before either value indexes anything (ReprojectMoved below: a
+//     value out of range reads index 0 and is dropped).
+//  2b g = geo[s], gp = geo_prev[sp]. All four floats of gp == g's (float ==: a
+//     NaN is unequal): Xp = X. Otherwise k = gp.r / g.r; o = X[j] - g.c[j];
+//     o = o * k; Xp[j] = gp.c[j] + o: the same surface point where the sphere
+//     was, rescaled if its radius changed. A zero or non-finite radius gives a
+//     non-finite Xp, and step 7 keeps every access inside the image.
+//  3  e[j] = Xp[j] - p_prev[j]; the rest of 3 and 4 - 7 unchanged.
+//  8  ... sphere_prev[q] == sp (not s) ...
+//
+// A motion with geo_prev equal to geo and the identity map is the plain
+// reprojection byte for byte; without a motion nothing above changes.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -109,20 +132,58 @@ MIRT_HD float reproject_dot3(const float a[3], const float b[3])   // trace.h do
 // What became of a pixel (mirt_history_stats counts them).
 enum { kReprojectSky = 0, kReprojectFresh = 1, kReprojectReused = 2 };
 
+// Steps 2a and 2b's loads for a pixel whose sphere is s: g, gp, sp, and ok =
+// both range tests passed. `mo` gives the motion: mo.num_spheres, mo.num_prev
+// (each >= 1), mo.has_index(), mo.index(i), mo.geo(i, out), mo.geo_prev(i, out)
+// at indices INSIDE the arrays. Every load is unconditional -- an index out of
+// range reads element 0 and ok is false -- so that the kernels issue geo[s]
+// and prev_index[s] together, then geo_prev[sp], ahead of the taps.
+struct ReprojectMoved {
+    float g[4], gp[4];
+    int32_t sp;
+    bool ok;
+};
+template <class Mo>
+MIRT_HD ReprojectMoved reproject_moved(const Mo& mo, int32_t s)
+{
+    ReprojectMoved m;
+    const bool in = s >= 0 && s < mo.num_spheres;
+    const int32_t si = in ? s : 0;
+    mo.geo(si, m.g);
+    m.sp = mo.has_index() ? mo.index(si) : si;
+    m.ok = in && m.sp >= 0 && m.sp < mo.num_prev;
+    mo.geo_prev(m.ok ? m.sp : 0, m.gp);
+    return m;
+}
+
+inline bool reproject_motion_valid(const mirt_sphere_motion* m, bool has_prev)
+{
+    return m && has_prev && m->geo && m->geo_prev && m->num_spheres >= 1 && m->num_prev >= 1 &&
+           (m->prev_index || m->num_prev == m->num_spheres);
+}
+
 // Pixel (x, y)'s new record, from its own rgba, t and s = sphere. has_prev
 // false: no previous frame (prev is not looked at). `at` gives the previous frame at an index INSIDE the
 // image: at.hist(q), at.t(q), at.sphere(q). TAPS: 1 or 4. *kind: one of the
-// three above.
-template <int TAPS, class At>
+// three above. moved: none (the plain reprojection), or the pixel's one
+// ReprojectMoved (the reprojection with a motion).
+template <int TAPS, class At, class... Moved>
 MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const ReprojectCam& prev, bool has_prev, const At& at,
                                         int width, int x, int y, uint32_t rgba, float t, int32_t s, int max_history,
-                                        float t_tolerance, int* kind)
+                                        float t_tolerance, int* kind, const Moved&... moved)
 {
+    static_assert(sizeof...(Moved) <= 1, "at most one ReprojectMoved");
     const float c[3] = {(float)(rgba & 0xffu) / 255.0f, (float)((rgba >> 8) & 0xffu) / 255.0f,
                         (float)((rgba >> 16) & 0xffu) / 255.0f};
     mirt_history_px fresh{c[0], c[1], c[2], 1};
     *kind = s < 0 ? kReprojectSky : kReprojectFresh;
     if (s < 0 || !has_prev) return fresh;
+    int32_t sp = s;   // 8 compares the previous frame's sphere with it
+    if constexpr (sizeof...(Moved) == 1) {
+        // 2a
+        if (!(moved.ok && ...)) return fresh;
+        sp = (moved.sp + ...);
+    }
     // 2: the hit point
     const float u0 = ((float)x / cur.wf - 0.5f) * cur.aspect;
     const float v0 = -((float)y / cur.hf - 0.5f);
@@ -139,7 +200,17 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
     // 3 .. 5: where the previous camera saw it, and how far away
     float e[3];
     for (int k = 0; k < 3; k++) {
-        const float X = cur.p[k] + d[k] * t;
+        float X = cur.p[k] + d[k] * t;
+        if constexpr (sizeof...(Moved) == 1) {
+            // 2b
+            const ReprojectMoved& m = (moved, ...);
+            if (!(m.gp[0] == m.g[0] && m.gp[1] == m.g[1] && m.gp[2] == m.g[2] && m.gp[3] == m.g[3])) {
+                const float kr = m.gp[3] / m.g[3];
+                float o = X - m.g[k];
+                o = o * kr;
+                X = m.gp[k] + o;
+            }
+        }
         e[k] = X - prev.p[k];
     }
     const float zf = reproject_dot3(e, prev.fwd);
@@ -193,7 +264,7 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
 #pragma unroll
 #endif
     for (int j = 0; j < TAPS; j++) {
-        if (!inside[j] || !(w[j] > 0.0f) || sq_[j] != s || hq[j].n < 1 || !(fabsf(l - tq[j]) <= bound)) continue;
+        if (!inside[j] || !(w[j] > 0.0f) || sq_[j] != sp || hq[j].n < 1 || !(fabsf(l - tq[j]) <= bound)) continue;
         sw_ = sw_ + w[j];
         sc[0] = sc[0] + hq[j].r * w[j];
         sc[1] = sc[1] + hq[j].g * w[j];

@@ -13,6 +13,16 @@
 // The counts of mirt_history_stats are one ballot and popcount per wave and
 // kind and one vector atomic add per wave into a three-word device record.
 // No loop, no workgroup waits on another.
+//
+// With a motion (mirt_reproject_motion*; reproject_kernel's MOTION instances)
+// a dependent chain stands in front of the gather: sphere[i] -> geo[s] (16 B)
+// and prev_index[s] (4 B), issued together -> geo_prev[sp] (one 16-byte load)
+// -> the taps. All of it is unconditional, as t's load is: a sky pixel and an
+// index out of range read element 0 and are dropped (reproject.h
+// reproject_moved), so the chain's loads are in flight while the pixel's
+// direction is computed. The sphere arrays are small beside the image (16 B x
+// spheres) and neighbouring lanes mostly see the same sphere: after the first
+// touch these are L2 / TCP hits. No scratch, no LDS, no loop.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -37,6 +47,9 @@ struct ReprojectState {
     int width = 0, height = 0;
     uint64_t scene_id = 0, frames = 0;
     mirt_camera cam{};        // the previous call's
+    uint64_t next_scene_id = 0;   // of the frame between frame_begin and frame_end
+    bool carry = false;       // frame_begin kept the history over a link: frame_end reprojects with its motion
+    bool carried = false;     // the last mirt_render_frame_reprojected did (mirt_history_motion_get)
 };
 
 void reproject_state_free(ReprojectState* st)
@@ -83,8 +96,29 @@ struct GlobalAt {
     __device__ int32_t sphere(size_t q) const { return sp[q]; }
 };
 
-template <int TAPS>
-__global__ void __launch_bounds__(kBlock) reproject_kernel(const ReprojectArgs a)
+// a mirt_sphere_motion of device pointers, as reproject_moved reads it: one 16-byte load per sphere
+struct MotionArgs {
+    const float4* g;
+    const float4* gp;
+    const int32_t* idx;
+    int32_t num_spheres, num_prev;
+    __device__ bool has_index() const { return idx != nullptr; }   // (uniform)
+    __device__ int32_t index(int32_t i) const { return idx[i]; }
+    __device__ void geo(int32_t i, float out[4]) const
+    {
+        const float4 v = g[i];
+        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    }
+    __device__ void geo_prev(int32_t i, float out[4]) const
+    {
+        const float4 v = gp[i];
+        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    }
+};
+
+// MOTION: none (the plain reprojection, whose code the pack leaves as it was), or one MotionArgs
+template <int TAPS, class... MOTION>
+__global__ void __launch_bounds__(kBlock) reproject_kernel(const ReprojectArgs a, const MOTION... mo)
 {
     const int bx = (int)(blockIdx.x % (unsigned)a.tiles_x), by = (int)(blockIdx.x / (unsigned)a.tiles_x);
     const int x = bx * kTileW + (int)(threadIdx.x % kTileW), y = by * kTileH + (int)(threadIdx.x / kTileW);
@@ -97,8 +131,9 @@ __global__ void __launch_bounds__(kBlock) reproject_kernel(const ReprojectArgs a
         // (t is used by hit pixels only; kept out of their branch so that the three loads are issued together)
         asm volatile("" : "+v"(t));
         const GlobalAt at{a.hist, a.t_prev, a.sphere_prev};
+        // (MOTION: the sphere's loads follow s at once, for every lane)
         const mirt_history_px h = reproject_pixel<TAPS>(a.cur, a.prev, a.has_prev != 0, at, a.width, x, y, px, t, s,
-                                                        a.max_history, a.t_tolerance, &kind);
+                                                        a.max_history, a.t_tolerance, &kind, reproject_moved(mo, s)...);
         a.hist_out[i] = h;
         if (a.out_rgb) {
             a.out_rgb[3 * i] = h.r;
@@ -128,7 +163,8 @@ unsigned tile_count(int width, int height, int* tiles_x)
 int reproject_enqueue(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
                       const uint32_t* d_rgba, const float* d_t, const int32_t* d_sphere, const mirt_history_px* d_hist,
                       const float* d_t_prev, const int32_t* d_sphere_prev, const mirt_reproject_params* p,
-                      mirt_history_px* d_hist_out, uint32_t* d_out, float* d_out_rgb, uint32_t* d_counts, hipStream_t s)
+                      mirt_history_px* d_hist_out, uint32_t* d_out, float* d_out_rgb, uint32_t* d_counts, hipStream_t s,
+                      const mirt_sphere_motion* motion = nullptr)   // (valid, device pointers; null: the plain form)
 {
     HIP_TRY(hipSetDevice(ctx_device(c)));
     if (int rc = ctx_launch_begin(c, s, false)) return rc;
@@ -152,7 +188,14 @@ int reproject_enqueue(mirt_ctx* c, int width, int height, const mirt_camera* cam
     a.counts = d_counts;
     if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 3 * sizeof(uint32_t), s));
     const unsigned g = tile_count(width, height, &a.tiles_x);
-    if (p->taps == 1)
+    if (motion) {
+        const MotionArgs mo{(const float4*)motion->geo, (const float4*)motion->geo_prev, motion->prev_index,
+                            motion->num_spheres, motion->num_prev};
+        if (p->taps == 1)
+            reproject_kernel<1><<<g, kBlock, 0, s>>>(a, mo);
+        else
+            reproject_kernel<4><<<g, kBlock, 0, s>>>(a, mo);
+    } else if (p->taps == 1)
         reproject_kernel<1><<<g, kBlock, 0, s>>>(a);
     else
         reproject_kernel<4><<<g, kBlock, 0, s>>>(a);
@@ -188,8 +231,8 @@ Parts state_parts(const ReprojectState* st, size_t n)
 
 // ---- the ctx's history (render.hip's mirt_render_frame_reprojected drives these two around its frame)
 
-int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, float** d_t, int32_t** d_sphere,
-                                const char* fn)
+int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, uint64_t link_from, float** d_t,
+                                int32_t** d_sphere, const char* fn)
 {
     ReprojectState** slot = ctx_reproject_state(c);
     if (!*slot) *slot = new (std::nothrow) ReprojectState();
@@ -198,7 +241,11 @@ int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t sce
         set_error("%s: out of host memory", fn);
         return MIRT_E_NOMEM;
     }
-    if (st->valid && (st->width != width || st->height != height || st->scene_id != scene_id)) {
+    // (link_from: the scene the slot's link to `scene_id` starts at, 0 without one the ctx may use)
+    st->carry = st->valid && st->width == width && st->height == height && st->scene_id != scene_id && link_from != 0 &&
+                st->scene_id == link_from;
+    st->carried = false;
+    if (st->valid && !st->carry && (st->width != width || st->height != height || st->scene_id != scene_id)) {
         st->valid = false;
         st->frames = 0;
     }
@@ -209,13 +256,17 @@ int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t sce
         st->d = nullptr;
         st->cap = 0;
         st->valid = false;
+        st->carry = false;
         st->frames = 0;
         HIP_TRY(hipMalloc(&st->d, bytes));
         st->cap = bytes;
     }
     st->width = width;
     st->height = height;
-    st->scene_id = scene_id;
+    // (a carried history keeps its own scene's id until the frame has been reprojected: should the frame fail, the
+    // next call meets the same link again, not records that index another scene's spheres)
+    st->next_scene_id = scene_id;
+    if (!st->carry) st->scene_id = scene_id;
     const Parts p = state_parts(st, n);
     const int dst = st->valid ? st->cur ^ 1 : 0;
     *d_t = p.t[dst];
@@ -224,17 +275,23 @@ int mirt::reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t sce
 }
 
 int mirt::reproject_frame_end(mirt_ctx* c, const mirt_camera* cam, const uint32_t* d_rgba,
-                              const mirt_reproject_params* params, const uint32_t** d_shown, hipStream_t s)
+                              const mirt_reproject_params* params, const mirt_sphere_motion* link_motion,
+                              const uint32_t** d_shown, hipStream_t s)
 {
     ReprojectState* st = *ctx_reproject_state(c);
     const Parts p = state_parts(st, (size_t)st->width * st->height);
     const int src = st->cur, dst = st->valid ? st->cur ^ 1 : 0;
     const bool prev = st->valid;
+    const bool carry = prev && st->carry && link_motion;
+    st->carry = false;
     st->valid = false;   // (until the launch below is enqueued)
     if (int rc = reproject_enqueue(c, st->width, st->height, cam, prev ? &st->cam : nullptr, d_rgba, p.t[dst],
                                    p.sphere[dst], prev ? p.rec[src] : nullptr, prev ? p.t[src] : nullptr,
-                                   prev ? p.sphere[src] : nullptr, params, p.rec[dst], p.display, nullptr, p.counts, s))
+                                   prev ? p.sphere[src] : nullptr, params, p.rec[dst], p.display, nullptr, p.counts, s,
+                                   carry ? link_motion : nullptr))
         return rc;
+    st->carried = carry;
+    st->scene_id = st->next_scene_id;
     st->cur = dst;
     st->valid = true;
     st->cam = *cam;
@@ -265,12 +322,39 @@ int mirt_reproject_device(mirt_ctx* c, int width, int height, const mirt_camera*
                              params, d_hist_out, d_out, d_out_rgb, nullptr, (hipStream_t)stream);
 }
 
-int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
-                   const mirt_rgba8* rgba, const float* t, const int32_t* sphere, const mirt_history_px* hist,
-                   const float* t_prev, const int32_t* sphere_prev, const mirt_reproject_params* params,
-                   mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb)
+int mirt_reproject_motion_device(mirt_ctx* c, int width, int height, const mirt_camera* cam,
+                                 const mirt_camera* cam_prev, const uint32_t* d_rgba, const float* d_t,
+                                 const int32_t* d_sphere, const mirt_history_px* d_hist, const float* d_t_prev,
+                                 const int32_t* d_sphere_prev, const mirt_reproject_params* params,
+                                 mirt_history_px* d_hist_out, uint32_t* d_out, float* d_out_rgb, void* stream,
+                                 const mirt_sphere_motion* motion)
 {
-    const char* fn = "mirt_reproject";
+    const char* fn = "mirt_reproject_motion_device";
+    if (!c) {
+        set_error("%s: null context", fn);
+        return MIRT_E_INVALID;
+    }
+    if (!reproject_args_valid(width, height, cam, cam_prev, d_rgba, d_t, d_sphere, d_hist, d_t_prev, d_sphere_prev,
+                              params, d_hist_out) ||
+        !reproject_motion_valid(motion, cam_prev != nullptr)) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    return reproject_enqueue(c, width, height, cam, cam_prev, d_rgba, d_t, d_sphere, d_hist, d_t_prev, d_sphere_prev,
+                             params, d_hist_out, d_out, d_out_rgb, nullptr, (hipStream_t)stream, motion);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the blocking forms: host pointers staged through one allocation (motion: null for mirt_reproject)
+int reproject_blocking(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                       const mirt_rgba8* rgba, const float* t, const int32_t* sphere, const mirt_history_px* hist,
+                       const float* t_prev, const int32_t* sphere_prev, const mirt_reproject_params* params,
+                       mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb, const mirt_sphere_motion* motion,
+                       const char* fn)
+{
     if (!c) {
         set_error("%s: null context", fn);
         return MIRT_E_INVALID;
@@ -286,7 +370,11 @@ int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, c
     const size_t n = (size_t)width * height;
     const size_t b_prev = hist ? n : 0, b_out = out ? 4 * n : 0, b_rgb = out_rgb ? 12 * n : 0;
     DevMem m;
-    HIP_TRY(hipMalloc(&m.p, 16 * n + 16 * b_prev + 12 * n + 8 * b_prev + b_out + b_rgb));
+    // (the motion's arrays last: 16-byte elements behind a multiple of 16 bytes, then the 4-byte map)
+    const size_t b_img = (16 * n + 16 * b_prev + 12 * n + 8 * b_prev + b_out + b_rgb + 15) & ~(size_t)15;
+    const size_t b_geo = motion ? 16 * (size_t)motion->num_spheres : 0, b_gp = motion ? 16 * (size_t)motion->num_prev : 0;
+    const size_t b_idx = motion && motion->prev_index ? 4 * (size_t)motion->num_spheres : 0;
+    HIP_TRY(hipMalloc(&m.p, b_img + b_geo + b_gp + b_idx));
     char* const d_ho = (char*)m.p;
     char* const d_h = d_ho + 16 * n;
     char* const d_px = d_h + 16 * b_prev;
@@ -296,6 +384,17 @@ int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, c
     char* const d_sp = d_tp + 4 * b_prev;
     char* const d_o = d_sp + 4 * b_prev;
     char* const d_rgb = d_o + b_out;
+    char* const d_geo = d_ho + b_img;
+    char* const d_gp = d_geo + b_geo;
+    char* const d_idx = d_gp + b_gp;
+    mirt_sphere_motion d_motion{};
+    if (motion) {
+        d_motion = mirt_sphere_motion{(const float*)d_geo, (const float*)d_gp, b_idx ? (const int32_t*)d_idx : nullptr,
+                                      motion->num_spheres, motion->num_prev};
+        HIP_TRY(hipMemcpyAsync(d_geo, motion->geo, b_geo, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_gp, motion->geo_prev, b_gp, hipMemcpyHostToDevice, s));
+        if (b_idx) HIP_TRY(hipMemcpyAsync(d_idx, motion->prev_index, b_idx, hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipMemcpyAsync(d_px, rgba, 4 * n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_t, t, 4 * n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_s, sphere, 4 * n, hipMemcpyHostToDevice, s));
@@ -308,7 +407,7 @@ int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, c
                                      (const int32_t*)d_s, hist ? (const mirt_history_px*)d_h : nullptr,
                                      hist ? (const float*)d_tp : nullptr, hist ? (const int32_t*)d_sp : nullptr, params,
                                      (mirt_history_px*)d_ho, out ? (uint32_t*)d_o : nullptr,
-                                     out_rgb ? (float*)d_rgb : nullptr, nullptr, s);
+                                     out_rgb ? (float*)d_rgb : nullptr, nullptr, s, motion ? &d_motion : nullptr);
     if (rc) {
         (void)hipStreamSynchronize(s);   // the copies in still read the caller's memory and write the staging
         return rc;
@@ -320,6 +419,39 @@ int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, c
     return MIRT_OK;
 }
 
+}  // namespace
+
+bool mirt::reproject_last_carried(mirt_ctx* c)
+{
+    const ReprojectState* st = *ctx_reproject_state(c);
+    return st && st->valid && st->carried;
+}
+
+extern "C" {
+
+int mirt_reproject(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                   const mirt_rgba8* rgba, const float* t, const int32_t* sphere, const mirt_history_px* hist,
+                   const float* t_prev, const int32_t* sphere_prev, const mirt_reproject_params* params,
+                   mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb)
+{
+    return reproject_blocking(c, width, height, cam, cam_prev, rgba, t, sphere, hist, t_prev, sphere_prev, params,
+                              hist_out, out, out_rgb, nullptr, "mirt_reproject");
+}
+
+int mirt_reproject_motion(mirt_ctx* c, int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                          const mirt_rgba8* rgba, const float* t, const int32_t* sphere, const mirt_history_px* hist,
+                          const float* t_prev, const int32_t* sphere_prev, const mirt_reproject_params* params,
+                          mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb, const mirt_sphere_motion* motion)
+{
+    const char* fn = "mirt_reproject_motion";
+    if (c && !mirt::reproject_motion_valid(motion, cam_prev != nullptr)) {
+        set_error("%s: invalid arguments", fn);
+        return MIRT_E_INVALID;
+    }
+    return reproject_blocking(c, width, height, cam, cam_prev, rgba, t, sphere, hist, t_prev, sphere_prev, params,
+                              hist_out, out, out_rgb, motion, fn);
+}
+
 int mirt_history_reset(mirt_ctx* c)
 {
     if (!c) {
@@ -328,6 +460,8 @@ int mirt_history_reset(mirt_ctx* c)
     }
     if (ReprojectState* st = *ctx_reproject_state(c)) {
         st->valid = false;
+        st->carry = false;
+        st->carried = false;
         st->frames = 0;
     }
     return MIRT_OK;

@@ -1,6 +1,6 @@
-// mirt_reproject_host: the reprojection of csrc/reproject.h on the host. No
-// HIP call, no ctx: the reference the device form is checked against, byte
-// for byte.
+// mirt_reproject_host and mirt_reproject_motion_host: the reprojection of
+// csrc/reproject.h on the host. No HIP call, no ctx: the reference the device
+// forms are checked against, byte for byte.
 #include <cstring>
 
 #include "internal.h"
@@ -28,6 +28,53 @@ struct HostAt {
     int32_t sphere(size_t q) const { return sp[q]; }
 };
 
+// a mirt_sphere_motion of host pointers, as reproject_moved reads it
+struct HostMotion {
+    const float *g, *gp;
+    const int32_t* idx;
+    int32_t num_spheres, num_prev;
+    bool has_index() const { return idx != nullptr; }
+    int32_t index(int32_t i) const { return idx[i]; }
+    void geo(int32_t i, float out[4]) const { std::memcpy(out, g + 4 * (size_t)i, 16); }
+    void geo_prev(int32_t i, float out[4]) const { std::memcpy(out, gp + 4 * (size_t)i, 16); }
+};
+
+// the loop of both host forms over VALID arguments (motion: null for the plain one)
+template <int TAPS>
+void reproject_image(int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev, const mirt_rgba8* rgba,
+                     const float* t, const int32_t* sphere, const HostAt& at, const mirt_reproject_params* params,
+                     mirt_history_px* hist_out, mirt_rgba8* out, float* out_rgb, const mirt_sphere_motion* motion)
+{
+    const ReprojectCam cur = reproject_cam(cam, width, height);
+    const ReprojectCam prv = cam_prev ? reproject_cam(cam_prev, width, height) : ReprojectCam{};
+    const bool prev = cam_prev != nullptr;
+    const HostMotion mo = motion ? HostMotion{motion->geo, motion->geo_prev, motion->prev_index, motion->num_spheres,
+                                              motion->num_prev}
+                                 : HostMotion{};
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            const size_t i = (size_t)y * width + x;
+            uint32_t px;
+            std::memcpy(&px, &rgba[i], 4);
+            int kind;
+            const mirt_history_px h =
+                motion ? reproject_pixel<TAPS>(cur, prv, prev, at, width, x, y, px, t[i], sphere[i], params->max_history,
+                                               params->t_tolerance, &kind, reproject_moved(mo, sphere[i]))
+                       : reproject_pixel<TAPS>(cur, prv, prev, at, width, x, y, px, t[i], sphere[i], params->max_history,
+                                               params->t_tolerance, &kind);
+            hist_out[i] = h;
+            if (out_rgb) {
+                out_rgb[3 * i] = h.r;
+                out_rgb[3 * i + 1] = h.g;
+                out_rgb[3 * i + 2] = h.b;
+            }
+            if (out) {
+                const uint32_t d = reproject_display(h);
+                std::memcpy(&out[i], &d, 4);
+            }
+        }
+}
+
 }  // namespace
 }  // namespace mirt
 
@@ -52,33 +99,32 @@ int mirt_reproject_host(int width, int height, const mirt_camera* cam, const mir
         set_error("mirt_reproject_host: invalid arguments");
         return MIRT_E_INVALID;
     }
-    const ReprojectCam cur = reproject_cam(cam, width, height);
-    const ReprojectCam prv = cam_prev ? reproject_cam(cam_prev, width, height) : ReprojectCam{};
-    const bool prev = cam_prev != nullptr;
     const HostAt at{hist, t_prev, sphere_prev};
-    for (int y = 0; y < height; y++)
-        for (int x = 0; x < width; x++) {
-            const size_t i = (size_t)y * width + x;
-            uint32_t px;
-            std::memcpy(&px, &rgba[i], 4);
-            int kind;
-            const mirt_history_px h =
-                params->taps == 1
-                    ? reproject_pixel<1>(cur, prv, prev, at, width, x, y, px, t[i], sphere[i], params->max_history,
-                                         params->t_tolerance, &kind)
-                    : reproject_pixel<4>(cur, prv, prev, at, width, x, y, px, t[i], sphere[i], params->max_history,
-                                         params->t_tolerance, &kind);
-            hist_out[i] = h;
-            if (out_rgb) {
-                out_rgb[3 * i] = h.r;
-                out_rgb[3 * i + 1] = h.g;
-                out_rgb[3 * i + 2] = h.b;
-            }
-            if (out) {
-                const uint32_t d = reproject_display(h);
-                std::memcpy(&out[i], &d, 4);
-            }
-        }
+    if (params->taps == 1)
+        reproject_image<1>(width, height, cam, cam_prev, rgba, t, sphere, at, params, hist_out, out, out_rgb, nullptr);
+    else
+        reproject_image<4>(width, height, cam, cam_prev, rgba, t, sphere, at, params, hist_out, out, out_rgb, nullptr);
+    return MIRT_OK;
+}
+
+int mirt_reproject_motion_host(int width, int height, const mirt_camera* cam, const mirt_camera* cam_prev,
+                               const mirt_rgba8* rgba, const float* t, const int32_t* sphere,
+                               const mirt_history_px* hist, const float* t_prev, const int32_t* sphere_prev,
+                               const mirt_reproject_params* params, mirt_history_px* hist_out, mirt_rgba8* out,
+                               float* out_rgb, const mirt_sphere_motion* motion)
+{
+    using namespace mirt;
+    if (!reproject_args_valid(width, height, cam, cam_prev, rgba, t, sphere, hist, t_prev, sphere_prev, params,
+                              hist_out) ||
+        !reproject_motion_valid(motion, cam_prev != nullptr)) {
+        set_error("mirt_reproject_motion_host: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    const HostAt at{hist, t_prev, sphere_prev};
+    if (params->taps == 1)
+        reproject_image<1>(width, height, cam, cam_prev, rgba, t, sphere, at, params, hist_out, out, out_rgb, motion);
+    else
+        reproject_image<4>(width, height, cam, cam_prev, rgba, t, sphere, at, params, hist_out, out, out_rgb, motion);
     return MIRT_OK;
 }
 

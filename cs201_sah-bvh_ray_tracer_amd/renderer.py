@@ -793,7 +793,7 @@ class Renderer:
             p.max_history, p.taps, p.t_tolerance = params
         return p
 
-    def reproject(self, cam, rgba, t, sphere, prev=None, params=None, rgb=False, out=None, stream=None):
+    def reproject(self, cam, rgba, t, sphere, prev=None, params=None, rgb=False, out=None, stream=None, motion=None):
         """The reprojection of mirt.h's mirt_reproject_params on a frame given
         as numpy arrays (mirt_reproject: blocking) or as torch tensors on the
         ctx's device (mirt_reproject_device: enqueued on `stream`, an integer
@@ -803,15 +803,21 @@ class Renderer:
         (H, W) abi.HISTORY records (tensors: (H, W, 4) float32 holding the same
         16 bytes). Returns (hist_out, display), or with rgb=True (hist_out,
         display, (H, W, 3) float32). `out` (device form): the uint8 tensor the
-        display goes to, which may be `rgba` itself."""
+        display goes to, which may be `rgba` itself. motion: None, or
+        (geo, geo_prev, prev_index) -- the spheres moved between the two frames
+        (mirt_sphere_motion, mirt_reproject_motion[_device]): geo (n, 4) and
+        geo_prev (m, 4) float32 {centre, radius}, prev_index (n,) int32 or None
+        for the identity; arrays or device tensors as the frame is."""
         p = self._reproject_params(params)
         h, w = sphere.shape
+        geo, geo_prev, prev_index = motion if motion is not None else (None, None, None)
         cam_prev, hist, t_prev, sphere_prev = prev if prev is not None else (None, None, None, None)
         cp = C.byref(cam_prev) if cam_prev is not None else None
         if not isinstance(sphere, np.ndarray):   # device tensors
             import torch
             for a, dtype in ((rgba, torch.uint8), (t, torch.float32), (sphere, torch.int32), (hist, torch.float32),
-                             (t_prev, torch.float32), (sphere_prev, torch.int32), (out, torch.uint8)):
+                             (t_prev, torch.float32), (sphere_prev, torch.int32), (out, torch.uint8),
+                             (geo, torch.float32), (geo_prev, torch.float32), (prev_index, torch.int32)):
                 if a is not None and not (a.is_cuda and a.is_contiguous() and a.dtype == dtype):
                     raise MirtError("reproject: tensors must be contiguous, on the device, uint8 / float32 / int32")
             hist_out = torch.empty((h, w, 4), dtype=torch.float32, device=sphere.device)
@@ -819,6 +825,15 @@ class Renderer:
                 out = torch.empty((h, w, 4), dtype=torch.uint8, device=sphere.device)
             out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=sphere.device) if rgb else None
             dp = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+            if motion is not None:
+                mo = abi.SphereMotion(geo.data_ptr(), geo_prev.data_ptr(),
+                                      prev_index.data_ptr() if prev_index is not None else None, geo.shape[0],
+                                      geo_prev.shape[0])
+                check(self.L.mirt_reproject_motion_device(self.h, w, h, C.byref(cam), cp, dp(rgba), dp(t), dp(sphere),
+                                                          dp(hist), dp(t_prev), dp(sphere_prev), C.byref(p),
+                                                          dp(hist_out), dp(out), dp(out_rgb), C.c_void_p(stream or 0),
+                                                          C.byref(mo)), "mirt_reproject_motion_device")
+                return (hist_out, out, out_rgb) if rgb else (hist_out, out)
             check(self.L.mirt_reproject_device(self.h, w, h, C.byref(cam), cp, dp(rgba), dp(t), dp(sphere), dp(hist),
                                                dp(t_prev), dp(sphere_prev), C.byref(p), dp(hist_out), dp(out),
                                                dp(out_rgb), C.c_void_p(stream or 0)), "mirt_reproject_device")
@@ -829,6 +844,16 @@ class Renderer:
         hist_out = np.zeros((h, w), abi.HISTORY)
         res = np.zeros((h, w, 4), np.uint8)
         out_rgb = np.zeros((h, w, 3), np.float32) if rgb else None
+        if motion is not None:
+            geo, geo_prev = cont(geo, np.float32), cont(geo_prev, np.float32)
+            prev_index = cont(prev_index, np.int32)
+            mo = abi.SphereMotion(geo.ctypes.data, geo_prev.ctypes.data,
+                                  prev_index.ctypes.data if prev_index is not None else None, geo.shape[0],
+                                  geo_prev.shape[0])
+            check(self.L.mirt_reproject_motion(self.h, w, h, C.byref(cam), cp, ptr(rgba), ptr(t), ptr(sphere), ptr(hist),
+                                               ptr(t_prev), ptr(sphere_prev), C.byref(p), ptr(hist_out), ptr(res),
+                                               ptr(out_rgb), C.byref(mo)), "mirt_reproject_motion")
+            return (hist_out, res, out_rgb) if rgb else (hist_out, res)
         check(self.L.mirt_reproject(self.h, w, h, C.byref(cam), cp, ptr(rgba), ptr(t), ptr(sphere), ptr(hist),
                                     ptr(t_prev), ptr(sphere_prev), C.byref(p), ptr(hist_out), ptr(res), ptr(out_rgb)),
               "mirt_reproject")
@@ -857,6 +882,13 @@ class Renderer:
         """mirt_history_stats as a dict (waits for the ctx's stream)."""
         st = abi.HistoryStats()
         check(self.L.mirt_history_stats_get(self.h, C.byref(st)), "mirt_history_stats_get")
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def history_motion(self):
+        """mirt_history_motion as a dict: the scene slot's link (abi.OPT_HISTORY_MOTION) and whether this ctx's last
+        reprojected frame was carried over one. No device call."""
+        st = abi.HistoryMotion()
+        check(self.L.mirt_history_motion_get(self.h, C.byref(st)), "mirt_history_motion_get")
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def history_read(self):

@@ -836,7 +836,8 @@ int mirt_render_frame_denoised(mirt_ctx *ctx, const mirt_camera *cam, const mirt
    current records, n = width * height of them (MIRT_E_INVALID without a
    history or for another n).
    Lens and jittered frames (their primary ray is not the pinhole's), shards,
-   mirt_multi, frames in flight and moving spheres are out of scope. */
+   mirt_multi and frames in flight are out of scope; moving spheres: the
+   mirt_reproject_motion forms and MIRT_OPT_HISTORY_MOTION below. */
 typedef struct mirt_history_px {
     float r, g, b;   /* the mean of n samples */
     int32_t n;       /* 0 = no history */
@@ -874,6 +875,86 @@ int mirt_render_frame_reprojected(mirt_ctx *ctx, const mirt_camera *cam, const m
 int mirt_history_reset(mirt_ctx *ctx);
 int mirt_history_stats_get(mirt_ctx *ctx, mirt_history_stats *out);
 int mirt_history_read(mirt_ctx *ctx, mirt_history_px *hist, size_t n);
+
+/* Reprojecting when the SPHERES moved between the two frames, and a history
+   that survives mirt_scene_refit_device / mirt_scene_update_device.
+   A motion: geo[num_spheres] is the scene the current frame's `sphere` plane
+   indexes, geo_prev[num_prev] the previous frame's scene, each sphere as four
+   floats {centre.x, .y, .z, radius} (MIRT_LAYOUT_GEO's first num_spheres
+   elements); prev_index[s] is the index in geo_prev of the sphere that is now
+   s (NULL: the identity). With a motion steps 2, 3 and 8 above become
+   (csrc/reproject.h; one binary32 operation each):
+     2  X = p + d * t, as before;
+     2a !(0 <= s < num_spheres): no history; sp = prev_index ? prev_index[s]
+        : s; !(0 <= sp < num_prev): no history (both compared before either
+        value indexes anything);
+     2b g = geo[s], gp = geo_prev[sp]; all four floats equal (float ==, a NaN
+        is unequal): Xp = X; else k = gp.r / g.r, o = X[j] - g.c[j], o = o * k,
+        Xp[j] = gp.c[j] + o -- the same surface point where the sphere was,
+        rescaled if its radius changed. A zero or non-finite radius gives a
+        non-finite Xp; step 7 keeps every access inside the image;
+     3  e = Xp - p_prev; the rest of 3 and 4 - 7 unchanged;
+     8  ... sphere_prev[q] == sp (not s) ...
+   A motion with geo_prev equal to geo and the identity map is the plain
+   reprojection byte for byte.
+   mirt_reproject_motion_host / _device / mirt_reproject_motion: the arguments
+   and contracts of their plain counterparts (stream ordering, aliasing, the
+   MIRT_E_INVALID cases before any device call, _device byte for byte the host
+   form) plus `motion`, whose pointers are host pointers for the host and
+   blocking forms and device pointers for _device. In addition MIRT_E_INVALID
+   for a NULL motion, geo or geo_prev, a count below 1, a NULL prev_index with
+   num_prev != num_spheres, and a motion without a previous frame.
+   MIRT_OPT_HISTORY_MOTION 1 (mirt_set_option) on the INSTALLING ctx: every path
+   of mirt_scene_refit_device[_ptr] and mirt_scene_update_device[_ptr] (the
+   host paths of declined inputs included) records a link on the scene slot:
+   the ids of the replaced and the installed scene, a device copy of the
+   replaced scene's geo array, and on the rebuild branch the permutation, in
+   device memory the slot keeps (it only grows, and goes with the slot). Every
+   other install -- the uploads, mirt_scene_build_device, any install by a ctx
+   with the option at 0 -- clears the link; a failed install leaves scene,
+   base cost and link as they were. With the option 1 on the RENDERING ctx,
+   mirt_render_frame_reprojected keeps a history whose scene id is the link's
+   `from` when the resident scene is the link's `to`, and reprojects that frame
+   with the motion {resident geo, the link's geo_prev, the link's map}. In
+   every other case (two installs since the last frame, a cleared link,
+   another width or height, mirt_history_reset) the history empties as before.
+   Option 0 (default): exactly the behaviour without the option, no device
+   work added to any install.
+   mirt_history_motion_get: the slot's link (ids 0: none; bytes: device memory
+   held for links; rebuilt: the link carries a permutation) and carried = this
+   ctx's last mirt_render_frame_reprojected used a link. No device call.
+   Out of scope: mirt_multi; shards; frames in flight (installs and reprojected
+   frames are blocking calls of the group's one host thread); lens and
+   jittered frames; composing several installs into one link; clamping the
+   history where shading changed because a NEIGHBOUR moved (shadows,
+   reflections): those samples are averaged as they are, as view-dependent
+   shading already is. */
+typedef struct mirt_sphere_motion {
+    const float *geo, *geo_prev;
+    const int32_t *prev_index;
+    int32_t num_spheres, num_prev;
+} mirt_sphere_motion;   /* 32 B */
+typedef struct mirt_history_motion {
+    uint64_t from_scene_id, to_scene_id, bytes;
+    int32_t rebuilt, carried;
+} mirt_history_motion;   /* 32 B */
+int mirt_reproject_motion_host(int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                               const mirt_rgba8 *rgba, const float *t, const int32_t *sphere,
+                               const mirt_history_px *hist, const float *t_prev, const int32_t *sphere_prev,
+                               const mirt_reproject_params *params, mirt_history_px *hist_out, mirt_rgba8 *out,
+                               float *out_rgb, const mirt_sphere_motion *motion);
+int mirt_reproject_motion_device(mirt_ctx *ctx, int width, int height, const mirt_camera *cam,
+                                 const mirt_camera *cam_prev, const uint32_t *d_rgba, const float *d_t,
+                                 const int32_t *d_sphere, const mirt_history_px *d_hist, const float *d_t_prev,
+                                 const int32_t *d_sphere_prev, const mirt_reproject_params *params,
+                                 mirt_history_px *d_hist_out, uint32_t *d_out, float *d_out_rgb, void *stream,
+                                 const mirt_sphere_motion *motion);
+int mirt_reproject_motion(mirt_ctx *ctx, int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                          const mirt_rgba8 *rgba, const float *t, const int32_t *sphere, const mirt_history_px *hist,
+                          const float *t_prev, const int32_t *sphere_prev, const mirt_reproject_params *params,
+                          mirt_history_px *hist_out, mirt_rgba8 *out, float *out_rgb,
+                          const mirt_sphere_motion *motion);
+int mirt_history_motion_get(mirt_ctx *ctx, mirt_history_motion *out);
 
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
@@ -1217,7 +1298,13 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        from an LDS tile with halo (1, default:
                                        MEASUREMENTS.md E) or by direct loads (0). Every other value is
                                        MIRT_E_INVALID. Speed only: the same bytes under either
-                                       setting. (25 is not assigned.) */ };
+                                       setting. (25 is not assigned.) */,
+       MIRT_OPT_HISTORY_MOTION = 27 /* 1 = refits and updates this ctx installs record a link on
+                                       the scene slot, and mirt_render_frame_reprojected on this
+                                       ctx carries its history over such a link
+                                       (mirt_history_motion_get); 0 (default) = every install
+                                       empties the history. Every other value is
+                                       MIRT_E_INVALID. */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back
