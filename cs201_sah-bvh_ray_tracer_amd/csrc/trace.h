@@ -453,6 +453,13 @@ struct SphRay {
 
 __device__ __forceinline__ SphRay sph_ray(const Ray& r) { return {r.ox, r.oy, r.oz, r.dx, r.dy, r.dz}; }
 
+// 4 d.d below the normal range, zero included (|d| below 2^-63; a NaN is not):
+// hit.c's quadratic then no longer describes where the ray meets the sphere --
+// t is off by any factor, or +inf for a == 0 -- so nothing geometric (Prune)
+// may be concluded from a hit of such a ray. prune_update's own guard is the
+// same threshold.
+__device__ __forceinline__ bool sub_normal_a4(float a4) { return a4 < 0x1p-126f; }
+
 // hit.c:19-39 without point/normal (computed once for the winner): the t a
 // hit would record if it could still become the closest (t <= best, the
 // later-DFS-leaf-wins tie rule), else -1.
@@ -656,7 +663,14 @@ __device__ __forceinline__ void closest_bvh_chunked(const DevScene& sc, const Ra
     uint32_t cur = 0;
     float bt = INFINITY;
     int bs = -1;
-    Prune pr = prune_start(sc, ray.ox, ray.oy, ray.oz);  // wave-uniform: one ray
+    // Pruning is a geometric argument (Prune: a recorded hit lies on its
+    // sphere), and hit.c's arithmetic stops being geometry once a = d.d leaves
+    // the normal range (|d| below 2^-63): with a subnormal a the recorded t is
+    // off by any factor, and with a == 0 every sphere whose leaf box passes and
+    // whose b does not underflow "hits" at t = +inf (tests/hostile_ray_cases.py,
+    // tiny_inf). Such a ray walks unpruned, as hit.c does. Wave-uniform: one ray.
+    const bool geometric = !sub_normal_a4(sp.a4());
+    Prune pr = geometric ? prune_start(sc, ray.ox, ray.oy, ray.oz) : prune_off();
     while (cur < end) {
         if (COUNT) cnt.steps++;
         const uint32_t base = cur;
@@ -694,13 +708,14 @@ __device__ __forceinline__ void closest_bvh_chunked(const DevScene& sc, const Ra
         }
         cur = c;
         const bool cand = ((visited >> lane) & 1) && t > 0.0f;
+        // (a candidate may hold t = +inf, which hit.c:105-108 records like any other t <= best)
         const float tmin = wave_min(cand ? t : INFINITY);
-        if (tmin <= bt && tmin < INFINITY) {
+        if (__ballot(cand) && tmin <= bt) {
             const uint64_t eq = __ballot(cand && t == tmin);
             const int last = 63 - __builtin_clzll(eq);
             bt = tmin;
             bs = __builtin_amdgcn_readlane(sph, last);
-            if (FAST && sc.prune) prune_update(pr, sc, ray.ox, ray.oy, ray.oz, sp.a4(), bt);
+            if (FAST && sc.prune && geometric) prune_update(pr, sc, ray.ox, ray.oy, ray.oz, sp.a4(), bt);
         }
         const uint64_t passed_leaves = __ballot(pass && leaf);
         if (COUNT) {  // uniform values: every lane holds the ray's totals
@@ -1530,9 +1545,11 @@ __device__ __forceinline__ void closest_hit(const DevScene& sc, const Ray& ray, 
     if (UNIFORM && FAST && sc.ordered) {
         // with pruning (sc.ordered implies it), a zero-component ray is held
         // to boxes around its own coordinate (pruned_any) and walks in the
-        // packet like any other
-        closest_packet_ordered<FAST, COUNT>(sc, ray, active, best_t, best_s, cnt);
-        gen = false;
+        // packet like any other -- unless its d.d is below the normal range,
+        // where that test's geometry does not hold (sub_normal_a4): those
+        // take the chunked walk, which then does not prune
+        gen = active && sub_normal_a4(sph_ray(ray).a4());
+        closest_packet_ordered<FAST, COUNT>(sc, ray, active && !gen, best_t, best_s, cnt);
     } else if (!UNIFORM && FAST && sc.wide && wstk) {
         // the bounce kernel's walk (wstk: a kWideStack-entry LDS column)
         const SlabRay sr = slab_ray(ray);

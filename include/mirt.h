@@ -1012,7 +1012,18 @@ int mirt_ctx_share_scene(mirt_ctx *ctx, mirt_ctx *owner);
 uint64_t mirt_ctx_scene_id(mirt_ctx *ctx);
 
 /* trace_ray (renderer.c:21-77) on n arbitrary rays; ray i uses RNG contract
-   pixel index i. */
+   pixel index i.
+   Rays are used as given -- here, in mirt_intersect_rays, mirt_any_hit_rays and
+   mirt_render_rays* alike, and a mirt_camera is not validated either:
+   components that are +-inf or NaN, a zero direction, a direction of any
+   magnitude and any origin are admitted and give hit.c's and renderer.c's
+   result for that ray, on every walk and schedule. That result need not be
+   geometry: for |d| near 2^-78, d.d underflows to zero and the reference's tree
+   walk records a hit with t = +inf, infinite point components and a NaN
+   normal (its brute-force loop, with a strict `<`, records none); the walks
+   record the same. hit, sphere, t and colours agree with the reference byte
+   for byte; a NaN in point or normal agrees as a NaN, not in sign or payload
+   (tests/test_hostile_rays_gpu.py). */
 int mirt_trace_rays(mirt_ctx *ctx, const mirt_ray *rays, int n, int depth, int use_bvh,
                     uint64_t seed, uint32_t sample, mirt_rgba8 *out);
 /* Same, ray i using RNG contract pixel index pixel0 + i (a caller's own pixel
