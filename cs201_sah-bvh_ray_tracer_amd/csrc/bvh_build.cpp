@@ -13,6 +13,14 @@
 //    <= i. Bin boxes/counts are exact; the left/right boxes and counts of
 //    every plane are therefore identical to the reference's, and the cost is
 //    then evaluated with the reference's exact operation sequence;
+//  * the monotone planes need lo <= hi on the axis. A node's box is inverted
+//    (hi < lo) on an axis exactly when its spheres have negative radii there
+//    (box c - r .. c + r, bvh.c:26-35; for r >= 0 rounding keeps c - r <= c + r,
+//    overflow gives -inf .. +inf, and a NaN is dropped by fmin / fmax). The
+//    planes then DECREASE with i, "left of plane i iff bin <= i" is false, and
+//    such an axis is evaluated by the reference's direct form instead
+//    (bvh.c:59-97): one pass over the node's spheres per plane, the same
+//    comparisons, boxes and counts by construction;
 //  * the in-place partition (bvh.c:172-201) is the reference's swap loop.
 // No FMA contraction (-ffp-contract=off): bvh.c:54-56,96,150-158 are
 // contraction-sensitive.
@@ -102,6 +110,23 @@ struct FlatBuilder {
 
     uint32_t cur = 0;  // final-array index (relative to this builder) of the next node
 
+    // bvh.c:59-97 as it stands: one candidate plane, one pass
+    float direct_cost(int lo, int hi, int axis, float split) const
+    {
+        Box left = box_empty(), right = box_empty();
+        int nl = 0, nr = 0;
+        for (int i = lo; i < hi; i++) {
+            if (centre(s[i], axis) < split) {
+                nl++;
+                box_add(left, s[i]);
+            } else {
+                nr++;
+                box_add(right, s[i]);
+            }
+        }
+        return sah_cost(nl, box_area(left), nr, box_area(right));
+    }
+
     void build(int lo, int hi, int depth)
     {
         const int me = (int)nodes.size();  // slot in `nodes`
@@ -125,6 +150,17 @@ struct FlatBuilder {
             float split[8];
             for (int i = 1; i < 8; i++)  // bvh.c:150/154/158
                 split[i] = split_plane(bounds.lo[axis], bounds.hi[axis], i);
+            if (bounds.hi[axis] < bounds.lo[axis]) {  // inverted box: decreasing planes, the direct form
+                for (int i = 1; i < 8; i++) {
+                    const float cost = direct_cost(lo, hi, axis, split[i]);
+                    if (cost < best_cost) {
+                        best_cost = cost;
+                        best_axis = axis;
+                        best_split = split[i];
+                    }
+                }
+                continue;
+            }
             Box bin_box[9];
             int bin_n[9] = {0};
             for (int k = 1; k <= 8; k++) bin_box[k] = box_empty();

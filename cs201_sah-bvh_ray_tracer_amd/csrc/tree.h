@@ -178,13 +178,17 @@ MIRT_HD inline float sah_cost(int nl, float la, int nr, float ra)
 // A sphere (its centre's and its radius' float words) the kernels decline and
 // the host takes instead: a NaN or an infinity, or a box coordinate fl(c -+ r)
 // that is -0.0 -- fmin(-0, +0) depends on operand order, and the kernels
-// combine in no fixed order.
+// combine in no fixed order -- or a negative radius: its box is inverted
+// (c - r > c + r), the split planes of a node of such spheres decrease, and
+// the kernels' bins assume that they increase (bvh_build.cpp has the direct
+// form for that axis).
 MIRT_HD inline bool sphere_declined(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t rad)
 {
     const uint32_t w[4] = {cx, cy, cz, rad};
     bool bad = false;
     for (int k = 0; k < 4; k++) bad |= (w[k] & 0x7f800000u) == 0x7f800000u;
     const float r = bits_float(rad);
+    bad |= r < 0.0f;
     for (int a = 0; a < 3; a++) {
         const float c = bits_float(w[a]);
         bad |= float_bits(c - r) == 0x80000000u || float_bits(c + r) == 0x80000000u;

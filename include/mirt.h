@@ -237,9 +237,10 @@ int mirt_scene_upload_flat(mirt_ctx *ctx, const mirt_sphere *spheres, int num_sp
    MIRT_E_INVALID before any HIP call, a HIP failure MIRT_E_DEVICE.
    Declined inputs: the kernels combine boxes in no fixed order, which gives the
    host's bits only where min/max are exact and symmetric. A range holding a NaN
-   or infinite centre or radius, or a sphere whose box fl(c - r), fl(c + r) has a
-   coordinate equal to -0.0 (fmin(-0, +0) depends on operand order), is
-   detected by the first pass; the host builder then runs on the untouched
+   or infinite centre or radius, a sphere whose box fl(c - r), fl(c + r) has a
+   coordinate equal to -0.0 (fmin(-0, +0) depends on operand order), or a
+   negative radius (its box is inverted: c - r > c + r, and the kernels' bins
+   need split planes that increase) is detected by the first pass; the host builder then runs on the untouched
    input (mirt_build_stats.on_device = 0), so the result is the same either way. */
 int mirt_bvh_build_flat_device(mirt_ctx *ctx, mirt_sphere *spheres, int start, int end, int depth,
                                mirt_node **out_nodes, int *out_count);
@@ -358,8 +359,8 @@ int mirt_bvh_refit_flat(mirt_node *nodes, int num_nodes, const mirt_sphere *sphe
    Declined inputs (mirt_refit_stats.on_device = 0) take the resident tree to
    the host, mirt_bvh_refit_flat and mirt_scene_upload_flat, with the same
    result: a NaN or infinite centre or radius in [s_0, end); a sphere box
-   coordinate equal to -0.0 (see mirt_bvh_build_flat_device); a resident scene
-   whose `ordered` flag is 0 -- the host refit then decides: a tree that is
+   coordinate equal to -0.0 or a negative radius (see
+   mirt_bvh_build_flat_device); a resident scene whose `ordered` flag is 0 -- the host refit then decides: a tree that is
    monotone but deeper than 62 levels is refit there, one that is not monotone
    is MIRT_E_INVALID.
    MIRT_E_NOSCENE without a resident scene; MIRT_E_INVALID if num_spheres is

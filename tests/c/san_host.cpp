@@ -123,6 +123,29 @@ int main(int argc, char** argv)
         check_layout(s, end, f);
     }
 
+    // negative radii: inverted boxes (c - r > c + r), so the builder's direct
+    // form runs (every fourth radius: mixed nodes; all of them: every node).
+    // The flat build equals the pointer-tree build, stays valid and lays out;
+    // large enough to fork, so the direct form runs on the child threads too
+    for (int every : {4, 1}) {
+        const int n = 40000;
+        std::vector<mirt_sphere> s1 = scene(false, n, 5);
+        for (int i = 0; i < n; i += every) s1[i].radius = -s1[i].radius;
+        std::vector<mirt_sphere> s2 = s1;
+        std::vector<mirt_node> f = flat_build(s1, 0, n, 0);
+        mirt_bvh_node* root = mirt_build_bvh_node(s2.data(), 0, n, 0);
+        CHECK(root != nullptr);
+        const int cnt = mirt_bvh_count(root);
+        std::vector<mirt_node> g((size_t)cnt);
+        CHECK(mirt_bvh_flatten(root, s2.data(), g.data(), cnt) == cnt);
+        CHECK(same(f, g));
+        mirt_free_bvh(root);
+        int inverted = 0;
+        for (const mirt_node& nd : f) inverted += nd.sphere < 0 && nd.bmax[0] < nd.bmin[0];
+        CHECK(every == 4 || inverted > 0);
+        check_layout(s1, n, f);
+    }
+
     // scene layouts of the degenerate shapes: no tree, nothing at all, a single
     // leaf, a small built tree, and coincident spheres (one-sided chains of
     // 0-sphere leaves down to the depth cap)

@@ -179,6 +179,10 @@ int main()
         CHECK(declined(3.0f, 5.0f, 7.0f, inf));     // an infinite radius
         CHECK(declined(-0.0f, 5.0f, 7.0f, 0.0f));   // c - r == -0.0
         CHECK(declined(3.0f, 5.0f, -0.0f, -0.0f));  // c + r == -0.0
+        CHECK(declined(3.0f, 5.0f, 7.0f, -1.0f));   // a negative radius: an inverted box
+        CHECK(declined(3.0f, 5.0f, 7.0f, -0x1p-149f));
+        CHECK(!declined(3.0f, 5.0f, 7.0f, -0.0f));  // r == -0.0 is not below zero: c -+ r == c
+        CHECK(!declined(3.0f, 5.0f, 7.0f, 0x1p127f));   // finite, whatever the box overflows to
         CHECK(!declined(1.0f, 5.0f, 7.0f, 1.0f));   // c - r == +0.0
         CHECK(!declined(3.0f, -5.0f, 7.0f, 0.5f));  // an ordinary sphere
     }
