@@ -1732,6 +1732,26 @@ __constant__ int kBoxEdge[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 
                                     {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
 __constant__ int kLineOffset[5][2] = {{0, 0}, {1, 0}, {0, 1}, {-1, 0}, {0, -1}};
 
+// A node's depth. The resident byte (MIRT_LAYOUT_NDEPTH) is exact below 255
+// and clamped there; a node that carries 255 finds its depth by the descent
+// from the root: the left child of inner node j is j + 1, the right one the
+// left one's skip, and `node` lies in the right subtree iff it is not before
+// it. cur only grows and stays <= node (an upload validates skip > index and
+// the nesting), so the walk ends after depth steps -- on trees deeper than 254
+// only.
+__device__ __forceinline__ uint32_t overlay_depth(const mirt_node* __restrict__ nodes,
+                                                  const uint8_t* __restrict__ ndepth, uint32_t node)
+{
+    uint32_t d = ndepth[node];
+    if (d < 255) return d;
+    d = 0;
+    for (uint32_t cur = 0; cur < node; d++) {
+        const uint32_t right = nodes[cur + 1].skip & MIRT_SKIP_MASK;
+        cur = node >= right ? right : cur + 1;
+    }
+    return d;
+}
+
 // one thread per (node, edge, offset): draw index (node * 12 + edge) * 5 + offset
 __global__ void overlay_lines_kernel(OverlayConst o, const mirt_node* __restrict__ nodes,
                                      const uint8_t* __restrict__ ndepth, uint32_t count, uint32_t* __restrict__ last)
@@ -1739,7 +1759,10 @@ __global__ void overlay_lines_kernel(OverlayConst o, const mirt_node* __restrict
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= count) return;
     const uint32_t node = id / 60, edge = (id / 5) % 12, off = id % 5;
-    if (o.max_levels >= 0 && ndepth[node] >= o.max_levels) return;
+    if (o.max_levels >= 0) {  // (the byte decides every level up to 255: the descent only past it)
+        const uint32_t d = o.max_levels > 255 ? overlay_depth(nodes, ndepth, node) : ndepth[node];
+        if (d >= (uint32_t)o.max_levels) return;
+    }
     const mirt_node nd = nodes[node];
     auto corner = [&](int k) {  // draw_aabb's corner order (:73-82)
         const int hx = (k == 1 || k == 2 || k == 5 || k == 6), hy = (k == 2 || k == 3 || k == 6 || k == 7), hz = k >= 4;
@@ -1772,15 +1795,15 @@ __global__ void overlay_lines_kernel(OverlayConst o, const mirt_node* __restrict
     }
 }
 
-__global__ void overlay_colour_kernel(const uint32_t* __restrict__ last, const uint8_t* __restrict__ ndepth,
-                                      size_t n, uint32_t* __restrict__ out)
+__global__ void overlay_colour_kernel(const uint32_t* __restrict__ last, const mirt_node* __restrict__ nodes,
+                                      const uint8_t* __restrict__ ndepth, size_t n, uint32_t* __restrict__ out)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t v = last[i];
     uint32_t c = 0xff000000u;  // SDL_RenderClear with (0, 0, 0, 255), main.c:342-343
     if (v) {
-        const uint32_t d = ndepth[(v - 1) / 60];
+        const uint32_t d = overlay_depth(nodes, ndepth, (v - 1) / 60);
         const uint32_t r = 255 - (d * 40) % 200, g = (d * 80) % 200, b = (d * 120) % 200;  // :107-110
         c = r | g << 8 | b << 16 | 180u << 24;
     }
@@ -4066,7 +4089,9 @@ int mirt_any_hit_rays(mirt_ctx* c, const mirt_ray* rays, int n, int use_bvh, int
 int mirt_bvh_overlay(mirt_ctx* c, const mirt_camera* cam, int width, int height, int max_levels, mirt_rgba8* out)
 {
     if (!ctx_ok(c, true, "mirt_bvh_overlay")) return MIRT_E_NOSCENE;
-    if (!cam || width <= 0 || height <= 0 || !out || (size_t)width * height > ((size_t)1 << 31)) {
+    // width, height <= 2^30: world_to_screen's range test forms width * 2 and height * 2 in int
+    if (!cam || width <= 0 || height <= 0 || !out || width > (1 << 30) || height > (1 << 30) ||
+        (size_t)width * height > ((size_t)1 << 31)) {
         set_error("mirt_bvh_overlay: invalid arguments");
         return MIRT_E_INVALID;
     }
@@ -4082,6 +4107,19 @@ int mirt_bvh_overlay(mirt_ctx* c, const mirt_camera* cam, int width, int height,
     o.height = height;
     o.max_levels = max_levels;
     const size_t pixels = (size_t)width * height;
+    // The image goes through the ctx's frame slab, on the ctx's stream: behind
+    // every frame enqueued on it and its copy out. A fresh frame's display
+    // left pending on a shared accumulation buffer (the lazy fold) lives in
+    // that slab: it is folded first, as before the slab is reallocated
+    // (enqueue_frame); and the slab grows only once the stream has left it.
+    if (c->acc && c->acc->pend_ctx == c) {
+        if (int rc = accum_materialize(c->acc, c->stream)) return rc;
+    }
+    if (c->slab_guard) {
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->slab_free, 0));
+        c->slab_guard = false;
+    }
+    if (c->out_cap < 4 * pixels + 4) HIP_TRY(hipStreamSynchronize(c->stream));
     int rc = ensure((void**)&c->d_overlay, &c->overlay_cap, 4 * pixels);
     if (!rc) rc = ensure((void**)&c->d_out, &c->out_cap, 4 * pixels + 4);
     if (rc) return rc;
@@ -4097,8 +4135,8 @@ int mirt_bvh_overlay(mirt_ctx* c, const mirt_camera* cam, int width, int height,
                                                                                      (uint32_t)lines, c->d_overlay);
         HIP_TRY(hipGetLastError());
     }
-    overlay_colour_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, c->stream>>>(c->d_overlay, sn->d_ndepth, pixels,
-                                                                                 c->d_out);
+    overlay_colour_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, c->stream>>>(c->d_overlay, sn->d_nodes32,
+                                                                                 sn->d_ndepth, pixels, c->d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->d_out, 4 * pixels, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -1025,6 +1025,15 @@ class Renderer:
         check(self.L.mirt_camera_rays(self.h, C.byref(cam), C.byref(fd), ptr(out)), "mirt_camera_rays")
         return out
 
+    def camera_rays_uv(self, cam, width, height, uv):
+        """get_camera_ray (ray.c:17-32) at caller-given (u, v): `uv` is (n, 2)
+        float32, the result n abi.RAY."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros(len(uv), abi.RAY)
+        check(self.L.mirt_camera_rays_uv(self.h, C.byref(cam), width, height, ptr(uv), len(uv), ptr(out)),
+              "mirt_camera_rays_uv")
+        return out
+
     def trace_ray(self, rays, depth=5, use_bvh=True, seed=1, sample=0):
         rays = np.ascontiguousarray(rays, abi.RAY)
         out = np.zeros((len(rays), 4), np.uint8)

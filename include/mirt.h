@@ -1160,12 +1160,30 @@ int mirt_camera_rays(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_des
    depth, over black; a pixel shows the last line drawn over it in the
    reference's order (pre-order nodes, draw_aabb's edge order). Lines are
    rasterised by Bresenham between the integer endpoints of world_to_screen
-   (the reference leaves that to SDL's backend). Writes width * height RGBA8. */
+   (the reference leaves that to SDL's backend). Writes width * height RGBA8.
+   A node's depth is its true depth in the tree, for every tree an upload
+   accepts, in the level test and in the colour alike: MIRT_LAYOUT_NDEPTH
+   keeps one byte per node clamped to 255, and a node that carries 255 takes
+   its depth from the descent from the root (O(depth) on trees deeper than 254
+   only). max_levels < 0 draws every node, 0 none; a max_levels above the
+   tree's depth equals -1. The camera's fields are used as given (no
+   camera_update): a corner behind z <= 0.1, outside [-W, 2W] x [-H, 2H] or
+   with a NaN coordinate drops its edges as the reference's tests do.
+   MIRT_E_NOSCENE without a scene (a scene without a tree gives the cleared
+   canvas); MIRT_E_INVALID for a NULL cam or out, for width or height <= 0 or
+   above 2^30 (world_to_screen forms 2 * width and 2 * height in int), and for
+   more than 2^31 pixels: checked before anything is allocated. Runs on the
+   ctx's stream, behind every frame enqueued on it, and reuses the ctx's frame
+   output slab: a frame in flight has been copied out before it is written. */
 int mirt_bvh_overlay(mirt_ctx *ctx, const mirt_camera *cam, int width, int height, int max_levels,
                      mirt_rgba8 *out);
 /* get_camera_ray (ray.c:17-32) at n caller-given (u, v) pairs (uv[2i],
    uv[2i+1]), for a frame of width x height (the reference's compile-time
-   WIDTH/HEIGHT, ray.c:18). */
+   WIDTH/HEIGHT, ray.c:18). (u, v) need not lie on the pixel grid, nor be
+   finite: direction = normalize(forward + horizontal * u + vertical * v) in
+   binary32 without contraction, whatever that gives. n = 0 returns MIRT_OK
+   and writes nothing; n < 0, a NULL cam, a NULL uv or out with n > 0, and
+   width or height <= 0 return MIRT_E_INVALID. Needs no scene. */
 int mirt_camera_rays_uv(mirt_ctx *ctx, const mirt_camera *cam, int width, int height, const float *uv, int n,
                         mirt_ray *out);
 
