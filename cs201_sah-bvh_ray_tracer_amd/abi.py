@@ -111,6 +111,12 @@ class DenoiseParams(C.Structure):
     _fields_ = [("passes", C.c_int32), ("normal_sharpness", C.c_int32), ("sigma_colour", C.c_float)]
 
 
+class DenoiseVarParams(C.Structure):
+    """mirt_denoise_var_params (mirt_denoise_var_params_default: 3, 3, 8, 4)"""
+    _fields_ = [("passes", C.c_int32), ("normal_sharpness", C.c_int32), ("sigma_lum", C.c_float),
+                ("min_history", C.c_int32)]
+
+
 class ReprojectParams(C.Structure):
     """mirt_reproject_params (mirt_reproject_params_default: 64, 4, 1/64)"""
     _fields_ = [("max_history", C.c_int32), ("taps", C.c_int32), ("t_tolerance", C.c_float)]
@@ -299,6 +305,15 @@ SIGNATURES = [
     ("mirt_reproject_motion_device", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     ("mirt_reproject_motion", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     ("mirt_history_motion_get", I, [P, P]),
+    ("mirt_denoise_var_params_default", None, [P]),
+    ("mirt_reproject_moments_host", I, [I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject_moments_device", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_reproject_moments", I, [P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    ("mirt_denoise_var_host", I, [I, I, P, P, P, P, P, P, P, P]),
+    ("mirt_denoise_var_device", I, [P, I, I, P, P, P, P, P, P, P, P, P]),
+    ("mirt_denoise_var", I, [P, I, I, P, P, P, P, P, P, P, P]),
+    ("mirt_render_frame_reprojected_denoised", I, [P, P, P, P, P, P, P, P]),
+    ("mirt_history_moments_read", I, [P, P, C.c_size_t]),
     ("mirt_ctx_wait", I, [P]),
     ("mirt_host_alloc", I, [C.c_size_t, C.POINTER(P)]),
     ("mirt_host_free", None, [P]),

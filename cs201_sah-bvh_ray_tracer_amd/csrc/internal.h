@@ -129,6 +129,27 @@ int denoise_enqueue(mirt_ctx* c, int width, int height, const uint32_t* d_rgba, 
 bool reproject_args_valid(int width, int height, const void* cam, const void* cam_prev, const void* rgba, const void* t,
                           const void* sphere, const void* hist, const void* t_prev, const void* sphere_prev,
                           const mirt_reproject_params* params, const void* hist_out);
+// What the mirt_reproject_moments forms check beyond that: a motion, if given,
+// is valid; m2_prev is null exactly when hist is; m2_out is given and is not
+// m2_prev.
+bool reproject_moments_valid(const void* hist, const mirt_sphere_motion* motion, bool has_prev, const void* m2_prev,
+                             const void* m2_out);
+// vfilter_host.cpp: what every form of mirt_denoise_var checks of its
+// arguments (pointers are only compared with null).
+bool vfilter_args_valid(int width, int height, const void* hist, const void* m2, const void* sphere,
+                        const mirt_denoise_var_params* params, const void* out, const void* out_rgb);
+// vfilter.hip: the variance-guided filter's scratch, kept on the ctx (created
+// by the first call, released by mirt_destroy).
+struct VfilterState;
+VfilterState** ctx_vfilter_state(mirt_ctx* c);
+void vfilter_state_free(VfilterState* st);
+// The filter of VALID arguments, all in device memory, enqueued on `stream`
+// under the name `fn` of the entry point it serves; vfilter_params_ok: the
+// parameters are valid (vfilter_host.cpp).
+int vfilter_enqueue(mirt_ctx* c, int width, int height, const mirt_history_px* d_hist, const float* d_m2,
+                    const int32_t* d_sphere, const float* d_normal, const mirt_denoise_var_params* params,
+                    uint32_t* d_out, float* d_out_rgb, float* d_var_out, ihipStream_t* stream, const char* fn);
+bool vfilter_params_ok(const mirt_denoise_var_params* params);
 // reproject.hip: the history of mirt_render_frame_reprojected, kept on the ctx
 // (created by the first call, released by mirt_destroy). begin: the history is
 // emptied if the image or the scene is not the one it was made of, and
@@ -144,11 +165,19 @@ void reproject_state_free(ReprojectState* st);
 // motion, device pointers. A history of exactly the scene link_from is kept
 // by begin, and end reprojects it with the motion; reproject_last_carried:
 // the last frame did.
+// moments (mirt_render_frame_reprojected_denoised): the records carry m2 in a
+// pair of planes allocated beside the history by the first such call; begin
+// empties a history without moments and gives *d_normal, where the frame
+// stores its normal plane; end carries m2 with the records. filter: the
+// variance-guided filter of the new records on `stream`, *d_filtered = its
+// display. Without moments begin and end proceed as they did and drop the flag.
 int reproject_frame_begin(mirt_ctx* c, int width, int height, uint64_t scene_id, uint64_t link_from, float** d_t,
-                          int32_t** d_sphere, const char* fn);
+                          int32_t** d_sphere, const char* fn, bool moments = false, float** d_normal = nullptr);
 int reproject_frame_end(mirt_ctx* c, const mirt_camera* cam, const uint32_t* d_rgba,
                         const mirt_reproject_params* params, const mirt_sphere_motion* link_motion,
-                        const uint32_t** d_shown, ihipStream_t* stream);
+                        const uint32_t** d_shown, ihipStream_t* stream, bool moments = false);
+int reproject_frame_filter(mirt_ctx* c, const mirt_denoise_var_params* vp, const uint32_t** d_filtered,
+                           ihipStream_t* stream, const char* fn);
 bool reproject_last_carried(mirt_ctx* c);
 // render.hip: what the install a refit or an update is about to make records
 // on the scene slot when the ctx has MIRT_OPT_HISTORY_MOTION 1:

@@ -2033,6 +2033,7 @@ struct mirt_ctx {
     void* d_guides = nullptr;   // mirt_render_frame_denoised: the frame's sphere and normal planes
     size_t guides_cap = 0;
     mirt::ReprojectState* reproject = nullptr;  // mirt_render_frame_reprojected's history (reproject.hip)
+    mirt::VfilterState* vfilter = nullptr;  // mirt_denoise_var*'s scratch (vfilter.hip)
     int history_motion = 0;     // MIRT_OPT_HISTORY_MOTION: installs record a link, reprojected frames carry over it
     // the install a refit / update is about to make (ctx_link_intent): what its link holds
     bool link_intent = false, link_rebuilt = false;
@@ -2859,6 +2860,7 @@ void mirt_destroy(mirt_ctx* c)
     mirt::build_state_free(c->build);
     mirt::denoise_state_free(c->denoise);
     mirt::reproject_state_free(c->reproject);
+    mirt::vfilter_state_free(c->vfilter);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
                     (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d, c->d_guides})
@@ -3170,6 +3172,7 @@ BuildState** ctx_build_state(mirt_ctx* c) { return &c->build; }
 DenoiseState** ctx_denoise_state(mirt_ctx* c) { return &c->denoise; }
 int ctx_denoise_tile(const mirt_ctx* c) { return c->denoise_tile; }
 ReprojectState** ctx_reproject_state(mirt_ctx* c) { return &c->reproject; }
+VfilterState** ctx_vfilter_state(mirt_ctx* c) { return &c->vfilter; }
 void ctx_link_intent(mirt_ctx* c, bool rebuilt, const int32_t* d_perm, const int32_t* h_perm)
 {
     c->link_intent = true;
@@ -3666,16 +3669,18 @@ int mirt_render_frame_denoised(mirt_ctx* c, const mirt_camera* cam, const mirt_l
 
 // ---- a frame and the display of its reprojected history (csrc/reproject.h)
 
-int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd,
-                                  const mirt_reproject_params* params, mirt_rgba8* out, mirt_rgba8* raw)
+// vp: null (mirt_render_frame_reprojected: `out` is the history's display), or the parameters of the
+// variance-guided filter (mirt_render_frame_reprojected_denoised: `out` is its display, `reprojected` the history's)
+static int frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd,
+                             const mirt_reproject_params* params, const mirt_denoise_var_params* vp, bool filtered,
+                             mirt_rgba8* out, mirt_rgba8* reprojected, mirt_rgba8* raw, const char* fn)
 {
-    const char* fn = "mirt_render_frame_reprojected";
     if (!c) {
         set_error("%s: null context", fn);
         return MIRT_E_INVALID;
     }
-    if (!cam || !frame_desc_valid(fd) || !reproject_params_valid(params) || !out || fd->accumulate != 0 ||
-        fd->samples > 1 || fd->num_shards != 1 || fd->jitter != 0 || fd->max_depth < 1) {
+    if (!cam || !frame_desc_valid(fd) || !reproject_params_valid(params) || (filtered && !vfilter_params_ok(vp)) ||
+        !out || fd->accumulate != 0 || fd->samples > 1 || fd->num_shards != 1 || fd->jitter != 0 || fd->max_depth < 1) {
         set_error("%s: invalid arguments", fn);
         return MIRT_E_INVALID;
     }
@@ -3692,9 +3697,11 @@ int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mir
     const bool linked = c->history_motion == 1 && lk.valid && lk.to == sn->id && lk.n == sn->num_spheres;
     const mirt_sphere_motion motion{(const float*)sn->d_geo, linked ? lk.geo_prev(lk.half) : nullptr,
                                     linked && lk.rebuilt ? lk.perm(lk.half) : nullptr, sn->num_spheres, lk.n};
-    if (int rc = reproject_frame_begin(c, fd->width, fd->height, sn->id, linked ? lk.from : 0, &d_t, &d_sphere, fn))
+    float* d_normal = nullptr;
+    if (int rc = reproject_frame_begin(c, fd->width, fd->height, sn->id, linked ? lk.from : 0, &d_t, &d_sphere, fn,
+                                       filtered, &d_normal))
         return rc;
-    c->planes = Planes{d_t, d_sphere, nullptr};
+    c->planes = Planes{d_t, d_sphere, d_normal};
     c->lone_frame = true;
     uint32_t* disp = nullptr;
     int rc = enqueue_frame(c, cam, fd, nullptr, &disp, fn);
@@ -3702,14 +3709,35 @@ int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mir
     c->planes = Planes{};
     if (rc) return rc;
     const uint32_t* shown = nullptr;
-    rc = reproject_frame_end(c, cam, disp, params, linked ? &motion : nullptr, &shown, c->stream);
+    rc = reproject_frame_end(c, cam, disp, params, linked ? &motion : nullptr, &shown, c->stream, filtered);
     if (rc) return rc;
+    // (the filter reads the new records and leaves them, and both displays, alone)
+    const uint32_t* d_filtered = nullptr;
+    if (filtered)
+        if ((rc = reproject_frame_filter(c, vp, &d_filtered, c->stream, fn))) return rc;
     const size_t row = (size_t)fd->width * 4;   // copies out as enqueue_host_frame's: rows x width
     if (raw) HIP_TRY(hipMemcpy2DAsync(raw, row, disp, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpy2DAsync(out, row, shown, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    if (filtered && reprojected)
+        HIP_TRY(hipMemcpy2DAsync(reprojected, row, shown, row, row, (size_t)fd->height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, row, filtered ? d_filtered : shown, row, row, (size_t)fd->height,
+                             hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->timed_recorded) HIP_TRY(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MIRT_OK;
+}
+
+int mirt_render_frame_reprojected(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd,
+                                  const mirt_reproject_params* params, mirt_rgba8* out, mirt_rgba8* raw)
+{
+    return frame_reprojected(c, cam, fd, params, nullptr, false, out, nullptr, raw, "mirt_render_frame_reprojected");
+}
+
+int mirt_render_frame_reprojected_denoised(mirt_ctx* c, const mirt_camera* cam, const mirt_frame_desc* fd,
+                                           const mirt_reproject_params* params, const mirt_denoise_var_params* vp,
+                                           mirt_rgba8* out, mirt_rgba8* reprojected, mirt_rgba8* raw)
+{
+    return frame_reprojected(c, cam, fd, params, vp, true, out, reprojected, raw,
+                             "mirt_render_frame_reprojected_denoised");
 }
 
 int mirt_ctx_wait(mirt_ctx* c)

@@ -71,10 +71,26 @@
 //
 // A motion with geo_prev equal to geo and the identity map is the plain
 // reprojection byte for byte; without a motion nothing above changes.
+//
+// With MOMENTS (mirt_reproject_moments*) a float plane m2 travels with the
+// records: the running mean of lum(sample)^2, lum(c) being L = 0.2126f * c[0];
+// L = L + 0.7152f * c[1]; L = L + 0.0722f * c[2] (reproject_lum). It is carried
+// exactly as the record's colour is; steps 1 - 11 are unchanged and these join:
+//
+//  1' Lc = lum(c); q2 = Lc * Lc.
+//  9' over the same valid taps, in the same order, from +0.0f:
+//     s2 = s2 + m2_prev[q] * w; then M2 = s2 / sw_. (m2_prev[q] is loaded with
+//     the tap's other loads, before any is used.)
+// 10' m2_out[i] = M2 + (q2 - M2) / (float)n_new. No history (sky, first frame,
+//     behind the camera, no valid tap): m2_out[i] = q2.
+//
+// The records, out and out_rgb are byte for byte those without the moments.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/mirt.h"
 #include "denoise.h"   // denoise_size_valid, denoise_display
@@ -129,6 +145,14 @@ MIRT_HD float reproject_dot3(const float a[3], const float b[3])   // trace.h do
     return s + a[2] * b[2];
 }
 
+// lum(c) of 1' (and of csrc/vfilter.h)
+MIRT_HD float reproject_lum(float r, float g, float b)
+{
+    float L = 0.2126f * r;
+    L = L + 0.7152f * g;
+    return L + 0.0722f * b;
+}
+
 // What became of a pixel (mirt_history_stats counts them).
 enum { kReprojectSky = 0, kReprojectFresh = 1, kReprojectReused = 2 };
 
@@ -166,16 +190,31 @@ inline bool reproject_motion_valid(const mirt_sphere_motion* m, bool has_prev)
 // false: no previous frame (prev is not looked at). `at` gives the previous frame at an index INSIDE the
 // image: at.hist(q), at.t(q), at.sphere(q). TAPS: 1 or 4. *kind: one of the
 // three above. moved: none (the plain reprojection), or the pixel's one
-// ReprojectMoved (the reprojection with a motion).
+// ReprojectMoved (the reprojection with a motion). MOMENTS: an `at` that also
+// has at.m2(q), the previous frame's m2, and a float* at.m2_new, which
+// receives the value of step 10'.
+template <class At, class = void>
+struct reproject_at_moments : std::false_type {};
+template <class At>
+struct reproject_at_moments<At, std::void_t<decltype(std::declval<const At&>().m2(size_t{}))>> : std::true_type {};
+
 template <int TAPS, class At, class... Moved>
 MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const ReprojectCam& prev, bool has_prev, const At& at,
                                         int width, int x, int y, uint32_t rgba, float t, int32_t s, int max_history,
                                         float t_tolerance, int* kind, const Moved&... moved)
 {
     static_assert(sizeof...(Moved) <= 1, "at most one ReprojectMoved");
+    constexpr bool MOMENTS = reproject_at_moments<At>::value;
     const float c[3] = {(float)(rgba & 0xffu) / 255.0f, (float)((rgba >> 8) & 0xffu) / 255.0f,
                         (float)((rgba >> 16) & 0xffu) / 255.0f};
     mirt_history_px fresh{c[0], c[1], c[2], 1};
+    float q2 = 0.0f;
+    if constexpr (MOMENTS) {
+        // 1'
+        const float Lc = reproject_lum(c[0], c[1], c[2]);
+        q2 = Lc * Lc;
+        *at.m2_new = q2;
+    }
     *kind = s < 0 ? kReprojectSky : kReprojectFresh;
     if (s < 0 || !has_prev) return fresh;
     int32_t sp = s;   // 8 compares the previous frame's sphere with it
@@ -245,6 +284,7 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
     mirt_history_px hq[TAPS];
     float tq[TAPS];
     int32_t sq_[TAPS];
+    float m2q[TAPS];
 #if defined(__clang__)
 #pragma unroll
 #endif
@@ -254,9 +294,11 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
         hq[j] = at.hist(q);
         tq[j] = at.t(q);
         sq_[j] = at.sphere(q);
+        if constexpr (MOMENTS) m2q[j] = at.m2(q);
     }
     // 8, 9
     float sw_ = 0.0f, sc[3] = {0.0f, 0.0f, 0.0f};
+    float s2 = 0.0f;   // (MOMENTS)
     int32_t nmin = 0;
     bool any = false;
     const float bound = t_tolerance * l;
@@ -269,6 +311,7 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
         sc[0] = sc[0] + hq[j].r * w[j];
         sc[1] = sc[1] + hq[j].g * w[j];
         sc[2] = sc[2] + hq[j].b * w[j];
+        if constexpr (MOMENTS) s2 = s2 + m2q[j] * w[j];
         nmin = any && nmin < hq[j].n ? nmin : hq[j].n;
         any = true;
     }
@@ -282,6 +325,11 @@ MIRT_HD mirt_history_px reproject_pixel(const ReprojectCam& cur, const Reproject
     out.g = m1 + (c[1] - m1) / nf;
     out.b = m2 + (c[2] - m2) / nf;
     out.n = n_new;
+    if constexpr (MOMENTS) {
+        // 9', 10'
+        const float M2 = s2 / sw_;
+        *at.m2_new = M2 + (q2 - M2) / nf;
+    }
     if (n_new > 1) *kind = kReprojectReused;
     return out;
 }

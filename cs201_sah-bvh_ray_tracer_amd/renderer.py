@@ -859,6 +859,143 @@ class Renderer:
               "mirt_reproject")
         return (hist_out, res, out_rgb) if rgb else (hist_out, res)
 
+    # ---- variance-guided filtering (the history carries E[L^2]; its variance steers an a-trous filter)
+    def reproject_moments(self, cam, rgba, t, sphere, prev=None, params=None, rgb=False, out=None, stream=None,
+                          motion=None):
+        """reproject with the second moment of luminance carried along
+        (mirt_reproject_moments on numpy arrays, mirt_reproject_moments_device
+        on tensors): the arguments of reproject, except that prev is None or
+        (cam_prev, hist, t_prev, sphere_prev, m2_prev) with m2_prev (H, W)
+        float32. Returns (hist_out, display, m2_out), or with rgb=True
+        (hist_out, display, (H, W, 3) float32, m2_out)."""
+        p = self._reproject_params(params)
+        h, w = sphere.shape
+        geo, geo_prev, prev_index = motion if motion is not None else (None, None, None)
+        cam_prev, hist, t_prev, sphere_prev, m2_prev = prev if prev is not None else (None,) * 5
+        cp = C.byref(cam_prev) if cam_prev is not None else None
+        if not isinstance(sphere, np.ndarray):   # device tensors
+            import torch
+            for a, dtype in ((rgba, torch.uint8), (t, torch.float32), (sphere, torch.int32), (hist, torch.float32),
+                             (t_prev, torch.float32), (sphere_prev, torch.int32), (out, torch.uint8),
+                             (geo, torch.float32), (geo_prev, torch.float32), (prev_index, torch.int32),
+                             (m2_prev, torch.float32)):
+                if a is not None and not (a.is_cuda and a.is_contiguous() and a.dtype == dtype):
+                    raise MirtError("reproject_moments: tensors must be contiguous, on the device, uint8 / float32 / "
+                                    "int32")
+            hist_out = torch.empty((h, w, 4), dtype=torch.float32, device=sphere.device)
+            m2_out = torch.empty((h, w), dtype=torch.float32, device=sphere.device)
+            if out is None:
+                out = torch.empty((h, w, 4), dtype=torch.uint8, device=sphere.device)
+            out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=sphere.device) if rgb else None
+            dp = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+            mo = None
+            if motion is not None:
+                mo = abi.SphereMotion(geo.data_ptr(), geo_prev.data_ptr(),
+                                      prev_index.data_ptr() if prev_index is not None else None, geo.shape[0],
+                                      geo_prev.shape[0])
+            check(self.L.mirt_reproject_moments_device(self.h, w, h, C.byref(cam), cp, dp(rgba), dp(t), dp(sphere),
+                                                       dp(hist), dp(t_prev), dp(sphere_prev), C.byref(p), dp(hist_out),
+                                                       dp(out), dp(out_rgb), C.c_void_p(stream or 0),
+                                                       C.byref(mo) if mo is not None else None, dp(m2_prev),
+                                                       dp(m2_out)), "mirt_reproject_moments_device")
+            return (hist_out, out, out_rgb, m2_out) if rgb else (hist_out, out, m2_out)
+        cont = lambda a, dtype: None if a is None else np.ascontiguousarray(a, dtype)   # noqa: E731
+        rgba, t, sphere = cont(rgba, np.uint8), cont(t, np.float32), cont(sphere, np.int32)
+        hist, t_prev, sphere_prev = cont(hist, abi.HISTORY), cont(t_prev, np.float32), cont(sphere_prev, np.int32)
+        m2_prev = cont(m2_prev, np.float32)
+        hist_out = np.zeros((h, w), abi.HISTORY)
+        m2_out = np.zeros((h, w), np.float32)
+        res = np.zeros((h, w, 4), np.uint8)
+        out_rgb = np.zeros((h, w, 3), np.float32) if rgb else None
+        mo = None
+        if motion is not None:
+            geo, geo_prev = cont(geo, np.float32), cont(geo_prev, np.float32)
+            prev_index = cont(prev_index, np.int32)
+            mo = abi.SphereMotion(geo.ctypes.data, geo_prev.ctypes.data,
+                                  prev_index.ctypes.data if prev_index is not None else None, geo.shape[0],
+                                  geo_prev.shape[0])
+        check(self.L.mirt_reproject_moments(self.h, w, h, C.byref(cam), cp, ptr(rgba), ptr(t), ptr(sphere), ptr(hist),
+                                            ptr(t_prev), ptr(sphere_prev), C.byref(p), ptr(hist_out), ptr(res),
+                                            ptr(out_rgb), C.byref(mo) if mo is not None else None, ptr(m2_prev),
+                                            ptr(m2_out)), "mirt_reproject_moments")
+        return (hist_out, res, out_rgb, m2_out) if rgb else (hist_out, res, m2_out)
+
+    @staticmethod
+    def _denoise_var_params(params):
+        """abi.DenoiseVarParams from one, from (passes, normal_sharpness, sigma_lum, min_history), or the defaults."""
+        if isinstance(params, abi.DenoiseVarParams):
+            return params
+        p = abi.DenoiseVarParams()
+        load().mirt_denoise_var_params_default(C.byref(p))
+        if params is not None:
+            p.passes, p.normal_sharpness, p.sigma_lum, p.min_history = params
+        return p
+
+    def denoise_var(self, hist, m2, sphere, normal=None, params=None, out=None, rgb=False, var=False, stream=None):
+        """The variance-guided filter of mirt.h's mirt_denoise_var_params on
+        records given as numpy arrays (mirt_denoise_var: blocking) or as torch
+        tensors on the ctx's device (mirt_denoise_var_device: enqueued on
+        `stream`, not waited for). hist: (H, W) abi.HISTORY (tensors:
+        (H, W, 4) float32 holding the same 16 bytes); m2: (H, W) float32;
+        sphere: (H, W) int32; normal: (H, W, 3) float32 or None. Returns the
+        (H, W, 4) uint8 display; with rgb=True and / or var=True a tuple
+        (display[, (H, W, 3) float32][, (H, W) float32 variances])."""
+        p = self._denoise_var_params(params)
+        h, w = sphere.shape
+        if not isinstance(sphere, np.ndarray):   # device tensors
+            import torch
+            for a, dtype in ((hist, torch.float32), (m2, torch.float32), (sphere, torch.int32),
+                             (normal, torch.float32), (out, torch.uint8)):
+                if a is not None and not (a.is_cuda and a.is_contiguous() and a.dtype == dtype):
+                    raise MirtError("denoise_var: tensors must be contiguous, on the device, float32 / int32 / uint8")
+            if out is None:
+                out = torch.empty((h, w, 4), dtype=torch.uint8, device=sphere.device)
+            out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=sphere.device) if rgb else None
+            var_out = torch.empty((h, w), dtype=torch.float32, device=sphere.device) if var else None
+            dp = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+            check(self.L.mirt_denoise_var_device(self.h, w, h, dp(hist), dp(m2), dp(sphere), dp(normal), C.byref(p),
+                                                 dp(out), dp(out_rgb), dp(var_out), C.c_void_p(stream or 0)),
+                  "mirt_denoise_var_device")
+            res = out
+        else:
+            hist, m2 = np.ascontiguousarray(hist, abi.HISTORY), np.ascontiguousarray(m2, np.float32)
+            sphere = np.ascontiguousarray(sphere, np.int32)
+            normal = None if normal is None else np.ascontiguousarray(normal, np.float32)
+            res = np.zeros((h, w, 4), np.uint8)
+            out_rgb = np.zeros((h, w, 3), np.float32) if rgb else None
+            var_out = np.zeros((h, w), np.float32) if var else None
+            check(self.L.mirt_denoise_var(self.h, w, h, ptr(hist), ptr(m2), ptr(sphere), ptr(normal), C.byref(p),
+                                          ptr(res), ptr(out_rgb), ptr(var_out)), "mirt_denoise_var")
+        got = (res,) + ((out_rgb,) if rgb else ()) + ((var_out,) if var else ())
+        return got if len(got) > 1 else res
+
+    def render_frame_reprojected_denoised(self, cam, width, height, params=None, var_params=None, reprojected=False,
+                                          raw=False, **frame_desc_args):
+        """render_frame_reprojected with the second moment carried along, and
+        the variance-guided filter of the new records
+        (mirt_render_frame_reprojected_denoised). Returns the filtered
+        (height, width, 4) uint8 display; with reprojected=True and / or
+        raw=True a tuple (filtered[, the history's display][, the one-sample
+        display])."""
+        fd = frame_desc(width, height, **frame_desc_args)
+        out = np.zeros((height, width, 4), np.uint8)
+        rep = np.zeros((height, width, 4), np.uint8) if reprojected else None
+        plain = np.zeros((height, width, 4), np.uint8) if raw else None
+        check(self.L.mirt_render_frame_reprojected_denoised(self.h, C.byref(cam), C.byref(fd),
+                                                            C.byref(self._reproject_params(params)),
+                                                            C.byref(self._denoise_var_params(var_params)), ptr(out),
+                                                            ptr(rep), ptr(plain)),
+              "mirt_render_frame_reprojected_denoised")
+        got = (out,) + ((rep,) if reprojected else ()) + ((plain,) if raw else ())
+        return got if len(got) > 1 else out
+
+    def history_moments_read(self):
+        """The current m2 plane, (height, width) float32 (mirt_history_moments_read)."""
+        st = self.history_stats()
+        out = np.zeros((st["height"], st["width"]), np.float32)
+        check(self.L.mirt_history_moments_read(self.h, ptr(out), out.size), "mirt_history_moments_read")
+        return out
+
     def render_frame_reprojected(self, cam, width, height, params=None, raw=False, **frame_desc_args):
         """render_frame (frame_desc's keyword arguments; one sample, one shard,
         no jitter, not accumulating) and the display of its history

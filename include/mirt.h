@@ -957,6 +957,127 @@ int mirt_reproject_motion(mirt_ctx *ctx, int width, int height, const mirt_camer
                           const mirt_sphere_motion *motion);
 int mirt_history_motion_get(mirt_ctx *ctx, mirt_history_motion *out);
 
+/* Filtering a reprojected frame by its own variance (spatio-temporal
+   variance-guided filtering). A pixel's noise varies across the image -- a
+   sphere facing the sky is calm, one among neighbours is not -- and a record
+   of 64 samples needs less help than a pixel disoccluded this frame. The
+   history therefore also carries the second moment of luminance, each pixel's
+   variance is estimated from it, and that variance sets the luminance weight
+   of an a-trous filter and is filtered along with the colour. Every operation
+   below is one correctly rounded binary32 operation, in this order
+   (csrc/reproject.h, csrc/vfilter.h); lum(c) is L = 0.2126f * c[0];
+   L = L + 0.7152f * c[1]; L = L + 0.0722f * c[2].
+   MOMENTS. m2, one float per pixel, is the running mean of lum(sample)^2,
+   carried exactly as the record's colour is. mirt_reproject_moments_host /
+   _device / mirt_reproject_moments take the arguments and contracts of the
+   mirt_reproject_motion form of the same kind (stream ordering, d_out
+   aliasing d_rgba, every MIRT_E_INVALID case before any device call), except:
+   motion may be NULL (the plain reprojection then runs); m2_prev is NULL
+   exactly when hist is; m2_out is required and must not be m2_prev. Steps
+   1 - 11 of mirt_reproject are unchanged -- hist_out, out and out_rgb are byte
+   for byte the plain or the motion form's -- and these join them:
+     1' Lc = lum(c); q2 = Lc * Lc;
+     9' over the same valid taps in the same order, from +0.0f:
+        s2 = s2 + m2_prev[q] * w; then M2 = s2 / sw_;
+    10' m2_out[i] = M2 + (q2 - M2) / (float)n_new; no history (sky, first
+        frame, behind the camera, no valid tap): m2_out[i] = q2.
+   VARIANCE, per pixel p of hist (the colour c = {r, g, b} and n), m2, sphere
+   and normal (three floats, may be NULL):
+     V1 Lp = lum(c_p). n_p >= min_history: vt = fmaxf(m2_p - Lp * Lp, 0.0f),
+        var_p = vt / (float)n_p;
+     V2 otherwise (every n_p <= 0 included) over the 7 x 7 window at spacing 1,
+        dy = -3 .. 3 outermost, dx = -3 .. 3 innermost, centre included, each
+        tap q inside the image with sphere[q] == sphere[p]: k = k + 1.0f,
+        S1 = S1 + Lq, S2 = S2 + Lq * Lq, Lq = lum(c_q), all from +0.0f; then
+        mu = S1 / k, var_p = fmaxf(S2 / k - mu * mu, 0.0f).
+     var_out (may be NULL) receives var_p.
+   FILTER. V3: pass i = 0 .. passes - 1 has spacing 2^i; taps, visiting order,
+   B, the same-sphere rule, the normal weight and the centre's 9/64 are
+   mirt_denoise's. With sigma_lum > 0 every other tap is also weighted by
+   luminance, Lp and Lq of this pass's input colours:
+        dl = Lp - Lq; g = dl * dl; den = sl2 * var_p; den = den + 1e-6f;
+        w = w * (1.0f / (1.0f + g / den)),  sl2 = sigma_lum * sigma_lum
+   (computed on the host; not rescaled per pass: the shrinking variance does
+   that). sw = sw + w, sc[ch] = sc[ch] + c_q[ch] * w, sv = sv + var_q * (w * w);
+   the pass writes the colour sc / sw and the variance sv / (sw * sw).
+   V4: out (RGBA8) and out_rgb as mirt_denoise's, at least one required. With
+   sigma_lum == 0 the colours are byte for byte mirt_denoise_host's on accum =
+   the records' three floats, frames = 1, the same passes and normal_sharpness,
+   sigma_colour = 0.
+   Non-finite data gives unspecified values, never an access outside the image
+   or the scratch.
+   mirt_denoise_var_host / _device / mirt_denoise_var have the contracts of
+   their mirt_denoise counterparts (the scratch is one allocation the ctx
+   keeps, which only grows; MIRT_OPT_DENOISE_TILE picks the passes' kernel,
+   either setting gives the same bytes). MIRT_E_INVALID, before any device
+   call: NULL ctx (not the host form), params, hist, m2 or sphere; no output;
+   width or height < 1 or width * height beyond 2^31; passes outside 1..5;
+   normal_sharpness outside 0..7; sigma_lum negative or not finite;
+   min_history outside 1..65536.
+   mirt_render_frame_reprojected_denoised: the loop in one blocking call. It
+   does everything mirt_render_frame_reprojected does -- the same checks (plus
+   MIRT_E_INVALID for invalid var params), the history emptied by the same
+   rules, MIRT_OPT_HISTORY_MOTION links honoured (through the moments form with
+   the link's motion), the PLANES bypass of the primary cache, colours and
+   accumulation buffer byte for byte the plain call's -- and also stores the
+   frame's normal plane and carries m2 with the records, in a ping-pong pair
+   the ctx keeps; then mirt_denoise_var runs on the new records. `out` receives
+   the filtered display, `reprojected` (may be NULL) what
+   mirt_render_frame_reprojected's `out` would have held, `raw` (may be NULL)
+   the one-sample display. The filter's output is not fed back: the records
+   after the call are the plain reprojected call's. The history is one per
+   ctx, and the ctx remembers whether its last reprojected frame carried
+   moments: a denoised call on a history without them empties it first; a plain
+   mirt_render_frame_reprojected on a history with them proceeds as it always
+   did and drops the flag. The m2 pair, the normal plane and the filtered
+   display are a separate allocation made by the first denoised call, which
+   mirt_history_stats.bytes counts once it exists; a ctx that never makes the
+   call allocates exactly what it did.
+   mirt_history_moments_read: the current m2 plane, n = width * height floats
+   (MIRT_E_INVALID without a history that carries moments, or for another n).
+   Out of scope: a 3 x 3 Gaussian prefilter of the variance; feeding the first
+   pass back into the history; clamping the history where a neighbour's motion
+   changed the shading; shards; mirt_multi; _async and frames in flight; lens
+   and jittered frames; 4K. */
+typedef struct mirt_denoise_var_params {
+    int32_t passes;            /* 1..5; pass i has tap spacing 2^i */
+    int32_t normal_sharpness;  /* 0..7 */
+    float sigma_lum;           /* >= 0, finite; 0 = no luminance weight */
+    int32_t min_history;       /* 1..65536: records of fewer samples take the spatial estimate */
+} mirt_denoise_var_params;     /* 16 B */
+void mirt_denoise_var_params_default(mirt_denoise_var_params *out);   /* 3, 3, 8, 4 */
+int mirt_reproject_moments_host(int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                                const mirt_rgba8 *rgba, const float *t, const int32_t *sphere,
+                                const mirt_history_px *hist, const float *t_prev, const int32_t *sphere_prev,
+                                const mirt_reproject_params *params, mirt_history_px *hist_out, mirt_rgba8 *out,
+                                float *out_rgb, const mirt_sphere_motion *motion, const float *m2_prev,
+                                float *m2_out);
+int mirt_reproject_moments_device(mirt_ctx *ctx, int width, int height, const mirt_camera *cam,
+                                  const mirt_camera *cam_prev, const uint32_t *d_rgba, const float *d_t,
+                                  const int32_t *d_sphere, const mirt_history_px *d_hist, const float *d_t_prev,
+                                  const int32_t *d_sphere_prev, const mirt_reproject_params *params,
+                                  mirt_history_px *d_hist_out, uint32_t *d_out, float *d_out_rgb, void *stream,
+                                  const mirt_sphere_motion *motion, const float *d_m2_prev, float *d_m2_out);
+int mirt_reproject_moments(mirt_ctx *ctx, int width, int height, const mirt_camera *cam, const mirt_camera *cam_prev,
+                           const mirt_rgba8 *rgba, const float *t, const int32_t *sphere, const mirt_history_px *hist,
+                           const float *t_prev, const int32_t *sphere_prev, const mirt_reproject_params *params,
+                           mirt_history_px *hist_out, mirt_rgba8 *out, float *out_rgb,
+                           const mirt_sphere_motion *motion, const float *m2_prev, float *m2_out);
+int mirt_denoise_var_host(int width, int height, const mirt_history_px *hist, const float *m2, const int32_t *sphere,
+                          const float *normal, const mirt_denoise_var_params *params, mirt_rgba8 *out,
+                          float *out_rgb, float *var_out);
+int mirt_denoise_var_device(mirt_ctx *ctx, int width, int height, const mirt_history_px *d_hist, const float *d_m2,
+                            const int32_t *d_sphere, const float *d_normal, const mirt_denoise_var_params *params,
+                            uint32_t *d_out, float *d_out_rgb, float *d_var_out, void *stream);
+int mirt_denoise_var(mirt_ctx *ctx, int width, int height, const mirt_history_px *hist, const float *m2,
+                     const int32_t *sphere, const float *normal, const mirt_denoise_var_params *params,
+                     mirt_rgba8 *out, float *out_rgb, float *var_out);
+int mirt_render_frame_reprojected_denoised(mirt_ctx *ctx, const mirt_camera *cam, const mirt_frame_desc *fd,
+                                           const mirt_reproject_params *params,
+                                           const mirt_denoise_var_params *var_params, mirt_rgba8 *out,
+                                           mirt_rgba8 *reprojected, mirt_rgba8 *raw);
+int mirt_history_moments_read(mirt_ctx *ctx, float *m2, size_t n);
+
 /* Download the ctx's accumulation buffer (row-major float3 of the shard),
    after every fold enqueued into it so far. */
 int mirt_accum_download(mirt_ctx *ctx, float *out, size_t count);
