@@ -145,6 +145,14 @@ HISTORY = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("n
 assert HISTORY.itemsize == 16
 
 
+class PrimaryScanStats(C.Structure):
+    """mirt_primary_scan_stats"""
+    _fields_ = [("scanned", C.c_uint64), ("bypassed", C.c_uint64), ("rebuilds", C.c_uint64), ("bytes", C.c_uint64),
+                ("tiles_scan", C.c_uint64), ("tiles_walk", C.c_uint64), ("tiles_empty", C.c_uint64),
+                ("chunks", C.c_uint64), ("leaves_tested", C.c_uint64), ("candidates", C.c_uint64), ("last", C.c_int32), ("reason", C.c_int32),
+                ("budget", C.c_int32), ("leaves", C.c_int32)]
+
+
 class PrimaryCacheStats(C.Structure):
     """mirt_primary_cache_stats"""
     _fields_ = [("hits", C.c_uint64), ("fills", C.c_uint64), ("bypassed", C.c_uint64), ("scene_id", C.c_uint64),
@@ -351,6 +359,9 @@ SIGNATURES = [
     ("mirt_primary_cache_stats_get", I, [P, P]),
     ("mirt_primary_cache_read", I, [P, P, P, C.c_size_t]),
     ("mirt_primary_cache_write", I, [P, P, P, C.c_size_t]),
+    ("mirt_primary_scan_stats_get", I, [P, P]),
+    ("mirt_pscan_camera", I, [P, I, I, P, P]),
+    ("mirt_pscan_records", I, [P, I, I, P, C.c_int64, P, P, P]),
     # include/mirt_dropin.h: the per-ray surface
     ("mirt_dropin_init", I, [I, I, I]),
     ("mirt_dropin_release", None, []),
@@ -405,6 +416,15 @@ PCACHE_REASON = {0: "", 1: "EMPTY", 2: "SCENE", 3: "CAMERA", 4: "GEOMETRY", 5: "
 # MIRT_PCACHE_LENS, which mirt.h writes as MIRT_PCACHE_RAYS + 1 (PCACHE_REASON holds the reasons written as literals)
 PCACHE_LENS = 10
 PCACHE_REASON_NAME = {**PCACHE_REASON, PCACHE_LENS: "LENS"}
+OPT_PRIMARY_SCAN = 28     # the camera pass by a depth-sorted tile scan: 0 off, 1 on, 2 automatic (default)
+OPT_PRIMARY_SCAN_BUDGET = 29   # chunks of 64 records a tile with a pixel still without a hit reads before it takes the packet walk (default 256)
+OPT_PRIMARY_SCAN_REBUILD = 30  # not a supported setting, a measurement hook: 1 = the scan's per-camera data rebuilt by every frame
+# mirt_primary_scan_stats: `last` (how the last frame met the scan) and `reason` (why it was a bypass)
+PSCAN_BYPASS, PSCAN_SCAN = 0, 1
+PSCAN_KIND = {PSCAN_BYPASS: "bypass", PSCAN_SCAN: "scan"}
+PSCAN_REASON = {0: "", 1: "OFF", 2: "CACHE", 3: "SCHEDULE", 4: "JITTER", 5: "PLANES", 6: "RAYS", 7: "LENS", 8: "TREE",
+                9: "SHARD", 10: "SIZE", 11: "CAMERA", 12: "SPARSE"}
+PSCAN_CAM = {0: "ok", 1: "nonfinite", 2: "degenerate", 3: "wide"}   # mirt_pscan_camera / mirt_pscan_records
 BOUNCE_STATS_WORDS = 23   # mirt.h MIRT_BOUNCE_STATS_WORDS
 TRAV_TILE, TRAV_WAVEFRONT = 0, 5
 BOX_FORM_SLAB, BOX_FORM_SLAB_BOX, BOX_FORM_CONS, BOX_FORM_CONS_BOUNCE, BOX_FORM_CONS_CAMERA = 0, 1, 2, 3, 4

@@ -109,6 +109,24 @@ int quality_device(ihipStream_t* stream, const mirt_node* d_nodes, int nn, int n
 // call sets it again).
 bool ctx_base_cost(const mirt_ctx* c, double* cost);
 void ctx_set_base_cost(mirt_ctx* c, double cost);
+// pscan.hip: the per-camera data of the primary scan (pscan.h),
+// built on `stream` into arrays the ctx owns: nl records sorted by key in
+// `rec`, and in `grid` ((ntx + 1) x (nty + 1) ints, row-major) the records
+// holding each tile. rec_in / key_in / key_out / planes (ntx + nty) / sort_tmp
+// (pscan_sort_bytes(nl) bytes) are scratch. Returns the hipError_t.
+struct PscanCam;
+struct PscanRec;
+struct PscanPlanes;
+struct PscanBuild {
+    PscanRec *rec_in, *rec;
+    float *key_in, *key_out;
+    PscanPlanes* planes;
+    int* grid;
+    void* sort_tmp;
+    size_t sort_bytes;
+};
+size_t pscan_sort_bytes(uint32_t nl);
+int pscan_build(const PscanCam& cam, const void* leaf_geo, uint32_t nl, const PscanBuild& b, ihipStream_t* stream);
 // denoise_host.cpp: what every form of mirt_denoise checks of its arguments
 // (pointers are only compared with null).
 bool denoise_args_valid(int width, int height, const void* rgba, const void* accum, int frames, const void* sphere,

@@ -21,6 +21,7 @@
 #include "denoise.h"
 #include "internal.h"
 #include "lens.h"
+#include "pscan.h"
 #include "reproject.h"
 #include "shard.h"
 #include "trace.h"
@@ -538,6 +539,152 @@ __global__ __launch_bounds__(256) MIRT_PRIMARY_ATTR void primary_kernel(DevScene
         base = __builtin_amdgcn_readlane(base, leader);
         if (push) queue[base + lanes_below(pm)] = rec;
     }
+}
+
+// ------------------------------------------------------------------------
+// The primary scan (MIRT_OPT_PRIMARY_SCAN; pscan.h): the camera
+// rays' closest hits of one slab found without the packet walk, into a slab of
+// the primary cache's format that primary_kernel<true, true, false, CacheRead>
+// then shades. For a tree whose boxes nest the closest hit is the least t, a
+// tie to the larger sphere index, among the leaves whose sphere_t<true> hits
+// and whose exact LeafBox passes slab_box<true> -- leaf_gate's rule,
+// whatever the order the leaves are met in.
+struct PscanDev {
+    const PscanRec* rec;   // nl records by ascending key
+    const int* grid;       // records holding tile (i, j) of the image: grid[j * gw + i]
+    uint32_t nl;
+    int gw;
+    float gx, gy, gz;      // G (pscan.h)
+    float* t;              // the slab: shard_rows * width each
+    int32_t* sphere;
+    uint32_t* wlist;       // [0]: tiles listed; then the tiles
+    unsigned long long* stats;  // kPscanSlots lines of {tiles done, tiles listed, tiles without a record, chunks, leaves, records holding the listed or done tiles}
+    int budget;            // chunks a tile with a lane still without a hit may read before it is listed
+};
+constexpr int kPscanSlots = 64, kPscanSlotWords = 8;
+constexpr uint32_t kPscanHardBudget = 1024;   // chunks any tile may read (64 Ki records: a guard, never met in MEASUREMENTS E)
+
+// One wave per 8x8 tile of the slab (primary_kernel's tiles of one frame),
+// lanes as primary_kernel's. The records come 64 at a time, one per lane, in
+// key order; the lanes whose rectangle holds the tile are tested one after
+// the other against all 64 rays by leaf_gate. Before a chunk the tile is done
+// when every live lane holds a hit nearer (strictly, pscan_depth_hi) than the
+// chunk's first key -- no record from there on can win or tie -- or when it has
+// met all the records that hold it. A tile not done within `budget` chunks
+// lists itself for pscan_walk_kernel and stores nothing.
+__global__ __launch_bounds__(256) void pscan_tile_kernel(DevScene sc, FrameConst f, PscanDev ps)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tiles_x = (f.width + 7) >> 3, tiles_y = (f.shard_rows + 7) >> 3;
+    const int tile = blockIdx.x * 4 + wave;
+    if (tile >= tiles_x * tiles_y) return;
+    const int ti = tile % tiles_x, tr = tile / tiles_x;
+    const int x = ti * 8 + (lane & 7), r = tr * 8 + (lane >> 3);
+    const bool alive = x < f.width && r < f.shard_rows;
+    const int y = alive ? shard_row_to_y(f, r) : 0;
+    const Ray ray = camera_ray(f, alive ? x : 0, y, f.sample);
+    // the tile's rows are one band of eight image rows (the classification)
+    const uint32_t tj = (uint32_t)__builtin_amdgcn_readfirstlane(y) >> 3;
+    const uint32_t want = (uint32_t)ps.grid[tj * ps.gw + ti];
+    const SlabRay sr = slab_ray(ray);
+    const SphRay sp = sph_ray(ray);
+    Prune pr = prune_start(sc, ray.ox, ray.oy, ray.oz);
+    const float dg = dot3(ray.dx, ray.dy, ray.dz, ps.gx, ps.gy, ps.gz);
+    float best_t = INFINITY;
+    int best_s = -1;
+    const uint32_t nchunks = (ps.nl + 63) >> 6;
+    uint32_t seen = 0, chunk = 0, tested = 0;
+    bool done = false;
+    for (;; chunk++) {
+        if (seen >= want || chunk >= nchunks) {
+            done = true;
+            break;
+        }
+        const uint32_t k = chunk * 64 + lane;
+        PscanRec rec{INFINITY, 0u, kPscanEmpty, kPscanEmpty};
+        if (k < ps.nl) rec = ps.rec[k];
+        const float z0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rec.z)));
+        const bool open = alive && !(best_s >= 0 && pscan_depth_hi(best_t, dg) < z0);
+        if (!__ballot(open)) {
+            done = true;
+            break;
+        }
+        // a tile whose live lanes all hold a hit ends by depth, within a few chunks of its last winner; one
+        // with a lane still without a hit (a sky pixel) can only end on its count, as far into the records as
+        // its farthest candidate lies: that tile is listed after `budget` chunks, any tile after kPscanHardBudget
+        if (chunk >= kPscanHardBudget || (chunk >= (uint32_t)ps.budget && __ballot(alive && best_s < 0))) break;
+        uint64_t m = __ballot(pscan_rec_holds(rec, (uint32_t)ti, tj));
+        seen += (uint32_t)__popcll(m);
+        tested += (uint32_t)__popcll(m);
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)rec.leaf, b);
+            const float4 g = load_geo_uniform(sc.leaf_geo, (int)li);
+            if (alive) leaf_gate(sc, sr, sp, pr, li, g, best_t, best_s);
+        }
+    }
+    if (done) {
+        if (alive) {
+            const size_t i = (size_t)r * f.width + x;
+            ps.t[i] = best_s >= 0 ? best_t : 0.0f;
+            ps.sphere[i] = best_s >= 0 ? best_s : -1;
+        }
+    } else if (lane == 0) {
+        ps.wlist[1 + atomicAdd(&ps.wlist[0], 1u)] = (uint32_t)tile;
+    }
+    if (lane == 0) {
+        unsigned long long* st = ps.stats + (size_t)(blockIdx.x % kPscanSlots) * kPscanSlotWords;
+        atomicAdd(&st[done ? (want ? 0 : 2) : 1], 1ull);
+        if (chunk) atomicAdd(&st[3], (unsigned long long)chunk);
+        if (tested) atomicAdd(&st[4], (unsigned long long)tested);
+        if (want) atomicAdd(&st[5], (unsigned long long)want);
+    }
+}
+
+// The listed tiles by the packet walk, into the same slab: a fixed grid
+// strided over the list, whose length is read here.
+template <bool BND>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MIRT_PRIMARY_WAVES))) void pscan_walk_kernel(DevScene sc, FrameConst f, PscanDev ps)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)ps.wlist[0]);
+    const int tiles_x = (f.width + 7) >> 3;
+    Counters cnt{0, 0, 0, 0, 0};
+    for (uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6); j < n; j += gridDim.x * 4) {
+        const int tile = __builtin_amdgcn_readfirstlane((int)ps.wlist[1 + j]);
+        const int x = (tile % tiles_x) * 8 + (lane & 7), r = (tile / tiles_x) * 8 + (lane >> 3);
+        const bool alive = x < f.width && r < f.shard_rows;
+        const int y = alive ? shard_row_to_y(f, r) : 0;
+        const Ray ray = camera_ray(f, alive ? x : 0, y, f.sample);
+        float t;
+        int s;
+        closest_packet_ordered<true, false, BND>(sc, ray, alive, t, s, cnt);
+        if (alive) {
+            const size_t i = (size_t)r * f.width + x;
+            ps.t[i] = s >= 0 ? t : 0.0f;
+            ps.sphere[i] = s >= 0 ? s : -1;
+        }
+    }
+}
+
+// The automatic mode's verdict on a scanned frame, from the frame's own
+// counters: a scene whose tiles that hold a record read more than
+// kPscanSparseChunks chunks each on average is one where most such tiles keep a
+// sky pixel and can only end on their count (MEASUREMENTS E: the walk is then
+// the faster camera pass). The scene's id goes to page-locked host memory,
+// where ps_classify finds it at a later enqueue without waiting for anything.
+constexpr unsigned long long kPscanSparseChunks = 16;
+__global__ void pscan_verdict_kernel(const unsigned long long* __restrict__ stats, unsigned long long* verdict,
+                                     unsigned long long scene_id)
+{
+    unsigned long long tiles = 0, chunks = 0;
+    for (int k = 0; k < kPscanSlots; k++) {
+        tiles += stats[k * kPscanSlotWords] + stats[k * kPscanSlotWords + 1];
+        chunks += stats[k * kPscanSlotWords + 3];
+    }
+    if (chunks > kPscanSparseChunks * tiles)
+        __hip_atomic_store(verdict, scene_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ------------------------------------------------------------------------
@@ -1952,6 +2099,37 @@ struct PrimaryCache {
     size_t pixels() const { return (size_t)key.shard_rows * key.width; }
 };
 
+// The primary scan of a ctx (MIRT_OPT_PRIMARY_SCAN): the
+// per-camera data of `key` (pscan.hip) and the per-frame slab, walk list and
+// counters, carved from one allocation that only ever grows (the rule of
+// d_planes: grown after waiting for the ctx's frames, never while they are in
+// flight). No events of its own, as the primary cache: frames of one ctx never
+// overlap.
+struct PrimaryScan {
+    int opt = 2;                 // 0 off, 1 on, 2 automatic
+    int budget = 256;            // MIRT_OPT_PRIMARY_SCAN_BUDGET: chunks of 64 records a tile with a sky pixel reads before it takes the walk
+    int always_rebuild = 0;      // MIRT_OPT_PRIMARY_SCAN_REBUILD: measurement hook, the per-camera data rebuilt every frame
+    void* d = nullptr;
+    size_t cap = 0;
+    bool valid = false;          // the per-camera data are those of `key`
+    PrimaryKey key{};
+    PscanCam cam{};
+    PscanBuild b{};
+    uint32_t nl = 0;
+    size_t sort_bytes = 0;       // pscan_sort_bytes(sort_nl)
+    uint32_t sort_nl = ~0u;
+    float* t = nullptr;
+    int32_t* sphere = nullptr;
+    uint32_t* wlist = nullptr;
+    unsigned long long* stats = nullptr;
+    // automatic mode: the id of the scene pscan_verdict_kernel found sparse (0: none), in page-locked host memory
+    // the device writes and ps_classify reads without a wait; d_verdict is its device address
+    unsigned long long* h_verdict = nullptr;
+    unsigned long long* d_verdict = nullptr;
+    uint64_t scanned = 0, bypassed = 0, rebuilds = 0;
+    int last = MIRT_PSCAN_BYPASS, reason = MIRT_PSCAN_NONE;
+};
+
 struct mirt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -2012,6 +2190,7 @@ struct mirt_ctx {
     void* d_planes = nullptr;   // planes of the blocking / async forms, copied to the host behind the frame
     size_t planes_cap = 0;
     PrimaryCache pc;            // MIRT_OPT_PRIMARY_CACHE: the camera rays' hits of a still camera
+    PrimaryScan ps;             // MIRT_OPT_PRIMARY_SCAN: the camera rays' hits by a depth-sorted tile scan
     mirt_camera frame_cam{};    // the camera of the frame being enqueued (pc's reason)
     int queue_order = 0;        // MIRT_OPT_QUEUE_ORDER: 0 auto (tile order for lone_frame), 1 octants, 2 tile order
     uint32_t* d_defer = nullptr;  // [count, list...]
@@ -2572,11 +2751,133 @@ int pc_classify(mirt_ctx* c, const FrameConst& f, bool diag, PrimaryUse* use)
     return MIRT_OK;
 }
 
+// MIRT_OPT_PRIMARY_SCAN: the frame being enqueued takes the tile scan
+// (*scan = true) or is a bypass with a recorded reason and runs the kernels
+// and arguments it ran before, decided here on the host. The
+// reasons are looked for in the order of the enum. Eligible is a frame for
+// which launch_render_body picks primary_kernel<true, true, *> without
+// jitter, planes, rays or a lens, on a bounded tree that nests (o_bound > 0:
+// finite coordinates, which pscan.h's margins assume), whose 8-row tiles are
+// bands of the image, with a camera pscan_camera accepts. A scanned frame
+// whose arrays outgrow the allocation waits for the ctx's frames, then grows
+// it: no allocation while the sizes stay.
+int ps_classify(mirt_ctx* c, const FrameConst& f, bool diag, bool* scan)
+{
+    PrimaryScan& ps = c->ps;
+    *scan = false;
+    const Scene* sn = scene_of(c);
+    const DevScene sc = dev_scene(c);
+    const bool packet = c->trav == kTravWavefront && f.use_bvh && f.depth >= 1 && !diag && c->fast_slab && sc.ordered &&
+                        f.num_rows > 0 && f.width > 0;
+    PscanFrame fr;
+    std::memcpy(fr.p, &f.px, 12 * sizeof(float));
+    fr.aspect = f.aspect; fr.wf = f.wf; fr.hf = f.hf; fr.width = f.width; fr.height = f.height;
+    // the caller's camera of this frame (the enqueuing calls record it): its fov, which f no longer shows
+    const bool own_cam = !std::memcmp(&c->frame_cam.position, &f.px, 12) && !std::memcmp(&c->frame_cam.forward, &f.fx, 12);
+    fr.fov = own_cam ? c->frame_cam.fov : NAN;
+    PscanCam cam{};
+    int why = !ps.opt ? MIRT_PSCAN_OFF : c->pc.on ? MIRT_PSCAN_CACHE : !packet ? MIRT_PSCAN_SCHEDULE
+              : f.jitter ? MIRT_PSCAN_JITTER : has_planes(c->planes) ? MIRT_PSCAN_PLANES : c->rays ? MIRT_PSCAN_RAYS
+              : c->lens ? MIRT_PSCAN_LENS : !(sc.wide && sn->prune_ok && sn->o_bound > 0.0f) ? MIRT_PSCAN_TREE
+              : !(f.row_block % 8 == 0 || (f.num_shards == 1 && f.lead_skip == 0)) ? MIRT_PSCAN_SHARD : 0;
+    if (!why && (f.width > 8 * kPscanMaxTiles || f.height > 8 * kPscanMaxTiles)) why = MIRT_PSCAN_SIZE;
+    if (!why && pscan_camera(fr, &cam) != PSCAN_CAM_OK) why = MIRT_PSCAN_CAMERA;
+    if (!why && ps.opt == 2 && ps.h_verdict && *(volatile unsigned long long*)ps.h_verdict == sn->id) why = MIRT_PSCAN_SPARSE;
+    if (why) {
+        if (why != MIRT_PSCAN_OFF) ps.bypassed++;
+        ps.last = MIRT_PSCAN_BYPASS;
+        ps.reason = why;
+        return MIRT_OK;
+    }
+    PrimaryKey k;
+    std::memset(&k, 0, sizeof k);
+    std::memcpy(k.cam, &f.px, sizeof k.cam);
+    k.aspect = f.aspect; k.wf = f.wf; k.hf = f.hf;
+    k.width = f.width; k.height = f.height; k.row_block = f.row_block; k.shard = f.shard;
+    k.num_shards = f.num_shards; k.lead_skip = f.lead_skip; k.shard_rows = f.shard_rows;
+    k.scene_id = sn->id;
+    if (!(ps.valid && !ps.always_rebuild && !std::memcmp(&k, &ps.key, sizeof k))) {
+        ps.valid = false;   // until the build is enqueued (launch_render_body)
+        const uint32_t nl = sn->num_leaves;
+        if (ps.sort_nl != nl) {
+            ps.sort_bytes = pscan_sort_bytes(nl);
+            ps.sort_nl = nl;
+            if (!ps.sort_bytes) return hip_fail(hipErrorUnknown, "rocprim::radix_sort_pairs (size query)");
+        }
+        const size_t pixels = (size_t)f.shard_rows * f.width;
+        const size_t tiles = (size_t)((f.width + 7) / 8) * ((f.shard_rows + 7) / 8);
+        const size_t n1 = nl ? nl : 1;
+        const size_t sizes[] = {sizeof(PscanRec) * n1, sizeof(PscanRec) * n1, 4 * n1, 4 * n1,
+                                sizeof(PscanPlanes) * (size_t)(cam.ntx + cam.nty),
+                                sizeof(int) * (size_t)(cam.ntx + 1) * (cam.nty + 1), ps.sort_bytes, 4 * pixels, 4 * pixels,
+                                8 * (size_t)kPscanSlots * kPscanSlotWords, 4 * (tiles + 1)};
+        size_t off[12] = {0};
+        for (int i = 0; i < 11; i++) off[i + 1] = (off[i] + sizes[i] + 255) & ~(size_t)255;
+        if (off[11] > ps.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+            if (int rc = ensure(&ps.d, &ps.cap, off[11])) return rc;
+        }
+        if (!ps.h_verdict) {   // once per ctx, with the first allocation above
+            HIP_TRY(hipHostMalloc((void**)&ps.h_verdict, 64, hipHostMallocMapped));
+            *ps.h_verdict = 0;
+            HIP_TRY(hipHostGetDevicePointer((void**)&ps.d_verdict, ps.h_verdict, 0));
+        }
+        char* d = (char*)ps.d;
+        ps.b = PscanBuild{(PscanRec*)(d + off[0]), (PscanRec*)(d + off[1]), (float*)(d + off[2]), (float*)(d + off[3]),
+                          (PscanPlanes*)(d + off[4]), (int*)(d + off[5]), d + off[6], ps.sort_bytes};
+        ps.t = (float*)(d + off[7]);
+        ps.sphere = (int32_t*)(d + off[8]);
+        ps.stats = (unsigned long long*)(d + off[9]);   // the walk list's count follows the counters' last line
+        ps.wlist = (uint32_t*)(d + off[10]);
+        ps.nl = nl;
+        ps.cam = cam;
+        ps.key = k;
+    }
+    ps.scanned++;
+    ps.last = MIRT_PSCAN_SCAN;
+    ps.reason = MIRT_PSCAN_NONE;
+    *scan = true;
+    return MIRT_OK;
+}
+
+// The scan pass of a frame ps_classify accepted, ahead of its camera-packet
+// kernel: the per-camera data if they are not the key's, the tile scan, the
+// walk of the tiles it listed. *pcu: the slab, for the cached form.
+int launch_scan(mirt_ctx* c, const DevScene& sc, const FrameConst& f, hipStream_t s, PrimaryUse* pcu)
+{
+    PrimaryScan& ps = c->ps;
+    if (!ps.valid) {
+        HIP_TRY((hipError_t)pscan_build(ps.cam, sc.leaf_geo, ps.nl, ps.b, s));
+        ps.valid = true;
+        ps.rebuilds++;
+    }
+    const int tiles = ((f.width + 7) / 8) * ((f.shard_rows + 7) / 8);
+    HIP_TRY(hipMemsetAsync(ps.stats, 0, 8 * (size_t)kPscanSlots * kPscanSlotWords, s));
+    HIP_TRY(hipMemsetAsync(ps.wlist, 0, 4, s));
+    const PscanDev dev{ps.b.rec, ps.b.grid, ps.nl, ps.cam.ntx + 1, ps.cam.g[0], ps.cam.g[1], ps.cam.g[2],
+                       ps.t, ps.sphere, ps.wlist, ps.stats, ps.budget};
+    pscan_tile_kernel<<<(tiles + 3) / 4, 256, 0, s>>>(sc, f, dev);
+    const int wblocks = std::min((tiles + 3) / 4, 8 * std::max(1, c->num_cus));
+    if (camera_bounded(c, f))
+        pscan_walk_kernel<true><<<wblocks, 256, 0, s>>>(sc, f, dev);
+    else
+        pscan_walk_kernel<false><<<wblocks, 256, 0, s>>>(sc, f, dev);
+    if (ps.opt == 2) pscan_verdict_kernel<<<1, 1, 0, s>>>(ps.stats, ps.d_verdict, scene_of(c)->id);
+    HIP_TRY(hipGetLastError());
+    pcu->how = MIRT_PCACHE_HIT;
+    pcu->t = ps.t;
+    pcu->sphere = ps.sphere;
+    return MIRT_OK;
+}
+
 int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float* d_acc, hipStream_t s, bool timed,
                        mirt_counts* d_counts, uint32_t* d_wave_stats, uint64_t* d_bdiag, AccumShare* chain)
 {
     PrimaryUse pcu;
     if (int rc = pc_classify(c, f, d_counts || d_wave_stats || d_bdiag, &pcu)) return rc;
+    bool scan = false;
+    if (int rc = ps_classify(c, f, d_counts || d_wave_stats || d_bdiag, &scan)) return rc;
     const int tiles = ((f.width + 7) / 8) * ((f.num_rows + 7) / 8);
     const int bw = c->block_waves;
     const int blocks = (tiles + bw - 1) / bw;
@@ -2665,6 +2966,8 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         BounceRec* queue = (BounceRec*)((char*)c->d_queue + kQCtlBytes);
         const int ptiles = f.samples >= 4 ? ((f.width + 3) / 4) * ((f.shard_rows + 3) / 4) * ((f.samples + 3) / 4)
                                           : tiles;
+        if (scan)
+            if (int rc2 = launch_scan(c, sc, f, s, &pcu)) return rc2;
         if (camera_bounded(c, f))
             launch_primary<true, true, true>((ptiles + 3) / 4, s, sc, f, d_out, d_acc, dfr, queue, qctl, 1, c->planes, pcu);
         else
@@ -2705,6 +3008,8 @@ int launch_render_body(mirt_ctx* c, const FrameConst& f, uint32_t* d_out, float*
         const int bblocks = c->bounce_blocks_opt ? c->bounce_blocks_opt : c->bounce_blocks;
         const size_t blds = bounce_lds_bytes(f.depth);
         const int oq = octant_queue(c);
+        if (scan)
+            if (int rc2 = launch_scan(c, sc, f, s, &pcu)) return rc2;
         if (rays)
             launch_ray_primary(c->fast_slab != 0, pblocks, s, sc, f, rays, d_out, d_acc, queue, qctl, c->planes);
         else if (lens)
@@ -2863,8 +3168,9 @@ void mirt_destroy(mirt_ctx* c)
     mirt::vfilter_state_free(c->vfilter);
     slot_leave(c);  // its frames are done: the slot's scene lives on with the other members
     for (void* p : {(void*)c->d_out, c->d_in, c->d_res, (void*)c->d_counts, (void*)c->d_defer, c->d_queue,
-                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d, c->d_guides})
+                    (void*)c->d_keys, (void*)c->d_overlay, c->d_planes, c->d_rays, c->pc.d, c->ps.d, c->d_guides})
         if (p) (void)hipFree(p);
+    if (c->ps.h_verdict) (void)hipHostFree(c->ps.h_verdict);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int k = 0; k < kPhaseRing; k++)
@@ -4481,6 +4787,32 @@ int mirt_set_option(mirt_ctx* c, int option, int value)
         c->pc.on = value;
         c->pc.hits = c->pc.fills = c->pc.bypassed = 0;   // counted since the option was last set to 1
         return MIRT_OK;
+    case MIRT_OPT_PRIMARY_SCAN: {
+        if (value < 0 || value > 2) break;
+        if (value == 0 && c->ps.d) {
+            // the frames that may still read or write the arrays, on whichever stream
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+            (void)hipFree(c->ps.d);
+            if (c->ps.h_verdict) (void)hipHostFree(c->ps.h_verdict);
+        }
+        const int budget = c->ps.budget, rebuild = c->ps.always_rebuild;
+        if (value == 0) c->ps = PrimaryScan{};
+        c->ps.opt = value;
+        c->ps.budget = budget;
+        c->ps.always_rebuild = rebuild;
+        c->ps.scanned = c->ps.bypassed = c->ps.rebuilds = 0;   // counted since the option was last set
+        return MIRT_OK;
+    }
+    case MIRT_OPT_PRIMARY_SCAN_BUDGET:
+        if (value < 1 || value > (1 << 24)) break;
+        c->ps.budget = value;
+        return MIRT_OK;
+    case MIRT_OPT_PRIMARY_SCAN_REBUILD:
+        if (value != 0 && value != 1) break;
+        c->ps.always_rebuild = value;
+        return MIRT_OK;
     default:
         break;
     }
@@ -4508,6 +4840,9 @@ int mirt_get_option(mirt_ctx* c, int option)
     if (option == MIRT_OPT_DEBUG_FAIL_CONFIRM) return c->debug_fail_confirm;
     if (option == MIRT_OPT_BUILD_FINISH) return c->build_finish;
     if (option == MIRT_OPT_PRIMARY_CACHE) return c->pc.on;
+    if (option == MIRT_OPT_PRIMARY_SCAN) return c->ps.opt;
+    if (option == MIRT_OPT_PRIMARY_SCAN_BUDGET) return c->ps.budget;
+    if (option == MIRT_OPT_PRIMARY_SCAN_REBUILD) return c->ps.always_rebuild;
     if (option == MIRT_OPT_DENOISE_TILE) return c->denoise_tile;
     if (option == MIRT_OPT_HISTORY_MOTION) return c->history_motion;
     if (option == MIRT_OPT_LEAF_BATCH) return leaf_batch(c) ? 1 : 0;  // in effect for the uploaded scene
@@ -4533,6 +4868,40 @@ int mirt_primary_cache_stats_get(mirt_ctx* c, mirt_primary_cache_stats* out)
     out->reason = pc.reason;
     out->width = pc.valid ? pc.key.width : 0;
     out->rows = pc.valid ? pc.key.shard_rows : 0;
+    return MIRT_OK;
+}
+
+int mirt_primary_scan_stats_get(mirt_ctx* c, mirt_primary_scan_stats* out)
+{
+    if (!c || !out) {
+        set_error("mirt_primary_scan_stats_get: invalid arguments");
+        return MIRT_E_INVALID;
+    }
+    const PrimaryScan& ps = c->ps;
+    *out = mirt_primary_scan_stats{};
+    out->scanned = ps.scanned;
+    out->bypassed = ps.bypassed;
+    out->rebuilds = ps.rebuilds;
+    out->bytes = ps.cap;
+    out->last = ps.last;
+    out->reason = ps.opt ? ps.reason : MIRT_PSCAN_OFF;
+    out->budget = ps.budget;
+    out->leaves = ps.valid ? ps.nl : 0;
+    if (ps.last != MIRT_PSCAN_SCAN || !ps.stats) return MIRT_OK;
+    // the last scanned frame's counters: the only device call, after its frames
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->launched && c->last_stream != c->stream) HIP_TRY(hipEventSynchronize(c->done));
+    unsigned long long h[kPscanSlots * kPscanSlotWords];
+    HIP_TRY(hipMemcpy(h, ps.stats, sizeof h, hipMemcpyDeviceToHost));
+    for (int k = 0; k < kPscanSlots; k++) {
+        out->tiles_scan += h[k * kPscanSlotWords];
+        out->tiles_walk += h[k * kPscanSlotWords + 1];
+        out->tiles_empty += h[k * kPscanSlotWords + 2];
+        out->chunks += h[k * kPscanSlotWords + 3];
+        out->leaves_tested += h[k * kPscanSlotWords + 4];
+        out->candidates += h[k * kPscanSlotWords + 5];
+    }
     return MIRT_OK;
 }
 

@@ -275,6 +275,18 @@ class HostBuffer:
             pass
 
 
+def primary_scan_stats(handle):
+    """mirt_primary_scan_stats of a mirt_ctx handle, as a dict with "last"
+    ("scan" / "bypass") and "reason" named. Waits for the ctx's frames when the
+    last one was scanned (the device counters are copied here only)."""
+    st = abi.PrimaryScanStats()
+    check(load().mirt_primary_scan_stats_get(handle, C.byref(st)), "mirt_primary_scan_stats_get")
+    out = _fields(st)
+    out["last"] = abi.PSCAN_KIND[st.last]
+    out["reason"] = abi.PSCAN_REASON[st.reason]
+    return out
+
+
 def primary_cache_stats(handle):
     """mirt_primary_cache_stats of a mirt_ctx handle (a Renderer's .h, or
     MultiRenderer.ctx(lane, rank)), as a dict with "last" and "reason" named."""
@@ -1080,6 +1092,10 @@ class Renderer:
         why the last frame was no hit ("" on a hit)."""
         return primary_cache_stats(self.h)
 
+    def primary_scan_stats(self):
+        """mirt_primary_scan_stats of this context (abi.OPT_PRIMARY_SCAN), as a dict."""
+        return primary_scan_stats(self.h)
+
     def primary_cache_read(self):
         """The cache's slab (mirt_primary_cache_read): (t float32, sphere int32),
         each of shape (rows, width)."""
@@ -1342,6 +1358,10 @@ class MultiRenderer:
     def primary_cache_stats(self, lane, rank):
         """mirt_primary_cache_stats of (lane, rank)'s context."""
         return primary_cache_stats(self.ctx(lane, rank))
+
+    def primary_scan_stats(self, lane, rank):
+        """mirt_primary_scan_stats of (lane, rank)'s context."""
+        return primary_scan_stats(self.ctx(lane, rank))
 
     def phase_log(self, lane, rank, n):
         """mirt_phase_log of (lane, rank)'s context: [primary_ms, bounce_ms] of its last n frames."""

@@ -1455,7 +1455,28 @@ enum { MIRT_OPT_TRAVERSAL = 1, MIRT_OPT_FAST_SLAB = 2, MIRT_OPT_BLOCK_WAVES = 3,
                                        ctx carries its history over such a link
                                        (mirt_history_motion_get); 0 (default) = every install
                                        empties the history. Every other value is
-                                       MIRT_E_INVALID. */ };
+                                       MIRT_E_INVALID. */,
+       MIRT_OPT_PRIMARY_SCAN = 28,  /* the camera pass finds each pixel's closest hit by a
+                                       depth-sorted scan of the leaves per 8x8 tile instead of
+                                       the packet walk, for the frames that qualify (below:
+                                       mirt_primary_scan_stats): 0 = off (waits for the ctx's
+                                       frames and releases the memory), 1 = on, 2 (default) =
+                                       automatic: on until a scanned frame of the scene shows
+                                       it to be sparse (SPARSE below). Every other value is
+                                       MIRT_E_INVALID; mirt_get_option reads back the stored
+                                       value. Speed only: the same bytes under every setting. */
+       MIRT_OPT_PRIMARY_SCAN_BUDGET = 29, /* the chunks of 64 leaf records that a tile of that scan
+                                       with a pixel still without a hit (a sky pixel: such a
+                                       tile can only end once it has met all its records) reads
+                                       before it takes the packet walk instead: 1 .. 2^24,
+                                       default 256 (MEASUREMENTS.md E). A tile whose pixels all
+                                       hold a hit ends by depth and reads up to 1,024 chunks
+                                       whatever this is. Speed only. */
+       MIRT_OPT_PRIMARY_SCAN_REBUILD = 30 /* NOT a supported setting: a measurement hook kept for
+                                       MEASUREMENTS.md E's "rebuilt every frame" figures, which
+                                       may go without notice. 1 = the scan's per-camera data are
+                                       rebuilt by every frame; 0 (default) = kept while the
+                                       camera, the frame geometry and the scene stay. */ };
 /* Traversal ids keep their first-release values (mirt 0.1: TILE 0, WAVEFRONT 5).
    ABI note: the mirt 0.2 header numbered WAVEFRONT 1; mirt_set_option accepts
    1 as a deprecated alias of MIRT_TRAV_WAVEFRONT (mirt_get_option reads back
@@ -1526,6 +1547,77 @@ int mirt_primary_cache_stats_get(mirt_ctx *ctx, mirt_primary_cache_stats *out);
    index out of bounds. */
 int mirt_primary_cache_read(mirt_ctx *ctx, float *t, int32_t *sphere, size_t n);
 int mirt_primary_cache_write(mirt_ctx *ctx, const float *t, const int32_t *sphere, size_t n);
+
+/* MIRT_OPT_PRIMARY_SCAN 1 or 2: every frame the ctx enqueues is classified on
+   the host when it is enqueued.
+     SCAN: the frame traces every camera ray, but not by the packet walk. Per
+       (camera, frame geometry, scene id) -- the primary cache's key, compared
+       bitwise -- the ctx keeps one 16-byte record per leaf (a depth key, the
+       leaf, the rectangle of 8x8 tiles its sphere can be hit from) sorted by
+       key, and per tile the number of records that hold it. Per frame one wave
+       per tile reads the records in key order, tests the leaves that hold its
+       tile with the walk's own sphere and box tests, and stops once every
+       pixel's hit is nearer than every record left or the tile's records are
+       exhausted; a tile that still has a pixel without a hit after
+       MIRT_OPT_PRIMARY_SCAN_BUDGET chunks (any tile after 1,024) is walked
+       instead. The hits go to a slab of the primary cache's format
+       and the camera-packet kernel's cached form shades them: the frame is the
+       walked frame byte for byte.
+     BYPASS: the frame runs exactly as with the option off. First reason found,
+       in this order: CACHE -- MIRT_OPT_PRIMARY_CACHE is 1; SCHEDULE, JITTER,
+       PLANES, RAYS, LENS -- as for the primary cache; TREE -- the tree does not
+       nest, is not ordered, or its coordinates are not bounded (beyond 6e4,
+       infinite or NaN); SHARD -- num_shards > 1 (or lead_skip) with a row_block
+       that is no multiple of 8; SIZE -- more than 65535 tiles along an axis;
+       CAMERA -- not finite, a basis whose triple product (forward x up).right
+       is zero or nearly so, or a field of view so wide that a corner ray is at
+       right angles to forward or beyond; SPARSE -- option 2 only: an earlier
+       scanned frame of this scene read more than 16 chunks per tile that holds
+       a record, as a scene does whose spheres leave sky in most tiles (such a
+       tile can only end on its count, and the walk is then faster:
+       MEASUREMENTS.md E). The verdict reaches the host without a wait, so the
+       frames enqueued before it lands are still scanned; it holds until another
+       scene is installed or the option is set again.
+   Memory: 8 bytes per shard pixel, 40 bytes per leaf plus the sort's scratch,
+   4 bytes per tile; it grows like the ctx's other buffers, after waiting for
+   the ctx's frames, never while the sizes stay. Option 0 and mirt_destroy
+   release it. */
+enum { MIRT_PSCAN_BYPASS = 0, MIRT_PSCAN_SCAN = 1 };
+enum { MIRT_PSCAN_NONE = 0, MIRT_PSCAN_OFF = 1, MIRT_PSCAN_CACHE = 2, MIRT_PSCAN_SCHEDULE = 3, MIRT_PSCAN_JITTER = 4,
+       MIRT_PSCAN_PLANES = 5, MIRT_PSCAN_RAYS = 6, MIRT_PSCAN_LENS = 7, MIRT_PSCAN_TREE = 8, MIRT_PSCAN_SHARD = 9,
+       MIRT_PSCAN_SIZE = 10, MIRT_PSCAN_CAMERA = 11, MIRT_PSCAN_SPARSE = 12 };
+typedef struct mirt_primary_scan_stats {
+    uint64_t scanned, bypassed;       /* frames classified since the option was last set (OFF is not counted) */
+    uint64_t rebuilds;                /* builds of the per-camera data since then */
+    uint64_t bytes;                   /* device memory the scan holds */
+    /* of the last frame enqueued, when it was a SCAN (else 0): */
+    uint64_t tiles_scan;              /* tiles holding a record that finished in the scan */
+    uint64_t tiles_walk;              /* tiles sent to the walk list */
+    uint64_t tiles_empty;             /* tiles no record holds */
+    uint64_t chunks;                  /* chunks of 64 records read */
+    uint64_t leaves_tested;           /* leaves tested against a tile's 64 rays */
+    uint64_t candidates;              /* records whose rectangle holds a tile, summed over the tiles that hold one */
+    int32_t  last;                    /* of the last frame enqueued: MIRT_PSCAN_SCAN / _BYPASS */
+    int32_t  reason;                  /* why it was a bypass (enum above); 0 on a scan */
+    int32_t  budget;                  /* MIRT_OPT_PRIMARY_SCAN_BUDGET */
+    int32_t  leaves;                  /* records of the per-camera data held; 0 when none */
+} mirt_primary_scan_stats;
+/* Waits for the ctx's frames and copies the counters only when the last frame
+   was a SCAN; otherwise no HIP call. MIRT_E_INVALID for a NULL ctx or out. */
+int mirt_primary_scan_stats_get(mirt_ctx *ctx, mirt_primary_scan_stats *out);
+/* The scan's per-camera arithmetic on the host (csrc/pscan.h, the code the
+   kernels compile), for tests; no ctx, no device. Both return MIRT_E_INVALID
+   for invalid arguments, else 0 for a camera the scan accepts or 1 (not
+   finite) / 2 (degenerate basis) / 3 (too wide) for one it bypasses.
+   mirt_pscan_camera: g[3] = the unit forward the depth keys are measured
+   along, *rho = the relative direction error allowed for camera_ray (either
+   may be NULL). mirt_pscan_records: for each of n spheres geo[4k..] = (centre,
+   radius): z[k] = its depth key, rect[4k..] = its tile rectangle i0, i1, j0, j1
+   (i0 > i1: empty), reach[k] (may be NULL) = R', the distance from the centre
+   within which every recorded hit lies. */
+int mirt_pscan_camera(const mirt_camera *cam, int width, int height, float *g, double *rho);
+int mirt_pscan_records(const mirt_camera *cam, int width, int height, const float *geo, int64_t n, float *z,
+                       int32_t *rect, double *reach);
 
 #ifdef __cplusplus
 }
